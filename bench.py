@@ -16,7 +16,8 @@ N > 1 : the path shards by MSM window: rank g owns windows [g*32/N, 
 One JSON line on rank 0 (see README / DESIGN.md for the field meanings).  `roofline` is for the dominant MSM kernel (level-0
 bucket add, k_add_level0) and `sumcheck.roofline` for the dominant round kernel of the prover, both timed with HIP events on
 the launch stream inside the timed runs; `cpu_baseline` is the C oracle (oracle/gkrmsm_oracle*.c, OpenMP) on this host,
-rank 0, N = 1 only.
+rank 0, N = 1 only.  `--dump-outputs DIR` writes what the last timed step returned (dump_outputs); the inputs are seeded, so two
+builds run with the same arguments can be compared file for file.
 """
 import argparse
 import ctypes as C
@@ -190,6 +191,18 @@ def claims_for(w_, y_log_, seed):
     return r, [ev(o) for o in outs], tape
 
 
+def dump_outputs(d, result, raw):
+    """--dump-outputs DIR: what the last timed MSM step handed its caller, bit for bit, as float64 .npy files -- every 256-bit field
+    element as its eight little-endian 32-bit words (each exact in a float64).
+      msm_result.npy     (2, 8)                   the MSM result, affine (x, y), canonical
+      window_points.npy  (3 (d + 1), windows, 8)  the window points as the library returns them (projective columns, Montgomery form)"""
+    os.makedirs(d, exist_ok=True)
+    xy = np.array([[(v >> (32 * i)) & 0xFFFFFFFF for i in range(8)] for v in result], dtype=np.float64)
+    np.save(os.path.join(d, "msm_result.npy"), xy)
+    words = np.ascontiguousarray(raw, dtype="<u8").view("<u4")
+    np.save(os.path.join(d, "window_points.npy"), words.astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -211,7 +224,11 @@ def main():
     ap.add_argument("--cpu-g1-outer-xlog", type=int, default=17)
     ap.add_argument("--concurrent-provers", type=int, default=3, help="N = 1: image-part proofs in flight from this many host threads (0 = skip)")
     ap.add_argument("--no-extra-shapes", action="store_true", help="N > 1: only the metric's x_logsize=20 line (skip weak / config D)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last timed MSM step "
+                    "returned as DIR/<name>.npy (rank 0; see dump_outputs); the inputs are seeded, the same on every run")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -526,7 +543,7 @@ def main():
             res["operand_broadcast_ms"] = round(bcast_ms, 2)
             res["operand_bytes"] = n * 96
         if keep:
-            return res, plan, d_pts, d_sc, sc, raw
+            return res, plan, d_pts, d_sc, sc, raw, result
         plan.close()
         del d_pts, d_sc
         L.gm_release_cached_memory()
@@ -534,8 +551,10 @@ def main():
         return res
 
     x_main = args.x_logsize if args.x_logsize is not None else 20
-    main_res, plan, d_pts, d_sc, sc, raw = msm_leg(x_main, args.steps, args.warmup, keep=True)
+    main_res, plan, d_pts, d_sc, sc, raw, result = msm_leg(x_main, args.steps, args.warmup, keep=True)
     x_log, n = x_main, 1 << x_main
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, result, raw)
 
     out = {
         "metric": "msm_points_per_sec", "value": main_res["value"], "unit": "points/s", "n_gpus": world,

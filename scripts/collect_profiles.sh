@@ -1,9 +1,9 @@
 #!/bin/bash
-# Runs ON THE GPU BOX (through gpurun): rocprofv3 kernel statistics of bench.py and the two PMC passes (FETCH_SIZE, WRITE_SIZE:
+# Runs on a machine with an MI355X: rocprofv3 kernel statistics of bench.py and the two PMC passes (FETCH_SIZE, WRITE_SIZE:
 # they do not fit one pass) for the MSM leg and for the image-part prover.  Outputs under gpurun_out/$1 (default r03_prof);
 # scripts/summarise_profiles.py turns them into profiles/rNN/*.
 set -o pipefail
-R=${GRAFT_REPO_ROOT:-/root/repo}
+R=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$R/gpurun_out/${1:-r04_prof}
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp

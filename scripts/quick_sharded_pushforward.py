@@ -56,7 +56,7 @@ if __name__ == "__main__":
     a = [int(v) for v in sys.argv[1:] if not v.startswith("--")]
     x_log, d_log, nbits, world = (a + [20, 8, 256, 4][len(a):])[:4]
     if threads:
-        os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
+        os.environ.setdefault("GM_SC_NO_PIPELINE", "1")   # rank threads on one device share its queues (tests/rank_threads.py)
         import queue
         import threading
         import torch

@@ -2,10 +2,10 @@
 // W processes share ONE device.  Every iteration: each process fills its buffer with a pattern of (rank, iteration) by a kernel,
 // synchronises its stream, meets the others at a barrier in shared host memory, copies the NEXT rank's buffer through its IPC
 // mapping (a kernel copy), checks the copy against the pattern on the device, meets the others again.  Printed: mismatching words.
-// With the runtime's default of four hardware queues per process the count stays 0; the question is what happens when every
-// process also holds many streams under GPU_MAX_HW_QUEUES=16 ("An oversubscribed device").
+// The count stays 0, also with every process holding many streams ("A second communicator re-opening the first
+// one's peers").
 //   hipcc -O2 --offload-arch=gfx950 -o ipc_visibility ipc_visibility.hip
-//   GPU_MAX_HW_QUEUES=16 ./ipc_visibility [processes 4] [extra streams 12] [iterations 200] [MiB 64]
+//   ./ipc_visibility [processes 4] [extra streams 12] [iterations 200] [MiB 64]
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>

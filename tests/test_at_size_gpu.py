@@ -587,7 +587,8 @@ def test_config_b_sharded_over_four_rank_threads_of_one_process():
            pushforward_time_inside_the_communicator_per_rank=[r[2]["clock"] for r in resp],
            seconds=round(time.perf_counter() - t_begin, 1),
            checked="every rank's image-part proof and pushforward argument equal the unsharded ones")
-    # (measured 1.46x and 1.47x; the bound only catches a path that fell off the fast one -- host-staged pulls, ordinary rounds everywhere)
+    # (rank threads on one device run the plain rounds, tests/rank_threads.py, and so does the unsharded proof of the same process:
+    # measured 1.78x and 1.48x; the bound only catches a path that fell off that one -- host-staged pulls, a rank waiting out time-outs)
     assert sharded <= 2.2 * alone and pf_sharded <= 2.2 * pf_alone
 
 

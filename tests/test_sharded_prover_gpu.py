@@ -114,11 +114,13 @@ def _worker_q(rank, world, q, port, x_log, d_log, nbits):
 
 def test_sharded_prove_image_part_world_8():
     """the target machine's rank count: 8 ranks x 2 windows (4 processes x 2 rank threads share the GPU, tests/rank_threads.py): the
-    last log2(8) = 3 rounds of every dense stage run replicated, the leader proves the bucket reduction for seven followers, the stage
-    kernel's agreement word is exchanged between 8"""
+    last log2(8) = 3 rounds of every dense stage run replicated, the leader proves the bucket reduction for seven followers.  Rank
+    threads on one device run the plain rounds (no stage kernel, so no per-layer agreement words in the count below): the dense
+    stages exchange their round sums down to one element per rank (GM_SC_SHARD_GATHER_LOG=0); world 8 at the default gather point
+    is covered by test_sharded_full_gpu.py"""
     sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
     from rank_threads import run_ranks
-    res = run_ranks(_worker_q, 8, (35100 + os.getpid() % 2000, 6, 2, 32), threads_per_proc=2)
+    res = run_ranks(_worker_q, 8, (35100 + os.getpid() % 2000, 6, 2, 32), threads_per_proc=2, env={"GM_SC_SHARD_GATHER_LOG": "0"})
     for rank, ok, calls, rounds, (unsharded, sharded, left) in res:
         assert calls > rounds // 2
 
