@@ -1773,19 +1773,27 @@ static uint32_t* alloc_host_writable_device_words() {
     uint32_t* ret = nullptr;
     if (!off && hipDeviceGetAttribute(&large_bar, hipDeviceAttributeIsLargeBar, dev_) == hipSuccess && large_bar) {
         uint32_t* p = nullptr;
-        if (hipExtMallocWithFlags((void**)&p, 4096, hipDeviceMallocFinegrained) == hipSuccess && p) {
-            // (the NULL stream only, not the device: another rank-thread of this process may have a kernel in flight that waits for
-            // a challenge its host will publish only after an exchange with THIS thread)
-            bool good = hipMemset(p, 0, 4096) == hipSuccess && hipStreamSynchronize(nullptr) == hipSuccess;
+        hipStream_t ps = nullptr;
+        if (hipExtMallocWithFlags((void**)&p, 4096, hipDeviceMallocFinegrained) == hipSuccess && p &&
+            hipStreamCreateWithFlags(&ps, hipStreamNonBlocking) == hipSuccess) {
+            // A stream of its own that does not synchronise with the NULL stream, and no wait on the device: the caller's stream may
+            // hold a pre-enqueued fold that waits for a challenge this thread publishes only after the launch (the first stage
+            // launch of a process behind a large pipelined round, on the NULL stream, sat there until the fold's wait timed out),
+            // and another rank-thread may have a kernel in flight that waits for an exchange with THIS thread
+            bool good = hipMemsetAsync(p, 0, 4096, ps) == hipSuccess && hipStreamSynchronize(ps) == hipSuccess;
             if (good) {
                 reinterpret_cast<volatile uint32_t*>(p)[1000] = 0x5eed1234u;   // probe: a host store the device must see
                 _mm_sfence();
                 uint32_t back = 0;
-                good = hipMemcpy(&back, p + 1000, 4, hipMemcpyDeviceToHost) == hipSuccess && back == 0x5eed1234u;
+                good = hipMemcpyAsync(&back, p + 1000, 4, hipMemcpyDeviceToHost, ps) == hipSuccess && hipStreamSynchronize(ps) == hipSuccess &&
+                       back == 0x5eed1234u;
                 reinterpret_cast<volatile uint32_t*>(p)[1000] = 0;
                 _mm_sfence();
             }
+            (void)hipStreamDestroy(ps);
             if (good) ret = p; else (void)hipFree(p);
+        } else if (p) {
+            (void)hipFree(p);
         }
     }
     (void)hipGetLastError();

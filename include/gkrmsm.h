@@ -107,7 +107,7 @@ int32_t gm_fn_shape(const gm_fn* f, int32_t* n_ins, int32_t* n_outs, int32_t* de
 
 /* ---------------------------------------------------------------- field batch ops (a1)
  * Elementwise Fr arithmetic over device arrays; replaces ark-ff operator calls inside the
- * reference's rayon loops (src/utils.rs:22-49).  op: 0 add, 1 sub, 2 mul, 3 neg(a), 4 inverse(a),
+ * reference's rayon loops (src/utils.rs:22-49).  op: 0 add, 1 sub, 2 mul, 3 neg(a), 4 inverse(a) = a^(p-2) (0 maps to 0),
  * 5 to-Montgomery(a), 6 from-Montgomery(a), 7 mul_by_a(a) = -5a, 8 mul_by_d(a). */
 int32_t gm_fr_batch(int32_t op, const uint64_t* d_a, const uint64_t* d_b, uint64_t* d_out, uint64_t n,
                     void* stream);

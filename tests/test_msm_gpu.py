@@ -206,6 +206,37 @@ def test_fr_batch_ops():
     assert all(x * y % F.P == 1 for x, y in zip(a[1:], inv[1:]))
     assert run(7) == [F.mul_by_a(x) for x in a]
     assert run(8) == [F.mul_by_d(x) for x in a]
+    # structured operands, as values: 0, 1, 2, p - 1, p - 2, 2^k and p - 2^k (k < 255), R mod p
+    s = [0, 1, 2, F.P - 1, F.P - 2, F.R] + [1 << k for k in range(255)] + [F.P - (1 << k) for k in range(255)]
+    s = [x % F.P for x in s]
+    t = s[1:] + s[:1]
+    m = len(s)
+    sa, sb, so = harness.to_dev(codec.to_mont_limbs(s)), harness.to_dev(codec.to_mont_limbs(t)), harness.dev_empty(m * 4)
+
+    def run_s(op, a_dev):
+        ffi.check(L.gm_fr_batch(op, C.c_void_p(a_dev.data_ptr()), C.c_void_p(sb.data_ptr()), C.c_void_p(so.data_ptr()),
+                                m, harness.cur_stream()))
+        return harness.to_host(so)
+    mont = lambda arr: codec.from_mont_limbs(arr)  # noqa: E731
+    assert mont(run_s(0, sa)) == [(x + y) % F.P for x, y in zip(s, t)]
+    assert mont(run_s(1, sa)) == [(x - y) % F.P for x, y in zip(s, t)]
+    assert mont(run_s(2, sa)) == [(x * y) % F.P for x, y in zip(s, t)]
+    assert mont(run_s(3, sa)) == [(-x) % F.P for x in s]
+    # inverse: x^(p - 2), which maps 0 to 0 (the convention of gm_fr_batch, include/gkrmsm.h)
+    assert mont(run_s(4, sa)) == [pow(x, F.P - 2, F.P) for x in s]
+    assert run(4)[0] == 0
+    assert mont(run_s(7, sa)) == [F.mul_by_a(x) for x in s]
+    assert mont(run_s(8, sa)) == [F.mul_by_d(x) for x in s]
+    # 5 / 6 act on the stored word itself: to-Montgomery w -> w R mod p, from-Montgomery w -> w R^-1 mod p; the same
+    # structured set taken as stored words (every one is below p), and the random words
+    R_INV = pow(F.R, -1, F.P)
+    for words in (s, [rng.next_fr() for _ in range(64)]):
+        dw = harness.to_dev(codec.ints_to_limbs(words))
+        n_w = len(words)
+        ffi.check(L.gm_fr_batch(5, C.c_void_p(dw.data_ptr()), None, C.c_void_p(so.data_ptr()), n_w, harness.cur_stream()))
+        assert codec.limbs_to_ints(harness.to_host(so)[: n_w * 4].reshape(n_w, 4)) == [w * F.R % F.P for w in words]
+        ffi.check(L.gm_fr_batch(6, C.c_void_p(dw.data_ptr()), None, C.c_void_p(so.data_ptr()), n_w, harness.cur_stream()))
+        assert codec.limbs_to_ints(harness.to_host(so)[: n_w * 4].reshape(n_w, 4)) == [w * R_INV % F.P for w in words]
 
 
 @pytest.mark.parametrize("name", ["msm_x4_d2_n12.json", "msm_x5_d3_n24.json"])
