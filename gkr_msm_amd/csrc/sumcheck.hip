@@ -18,6 +18,7 @@
 #include <immintrin.h>
 #include <chrono>
 #include <condition_variable>
+#include <type_traits>
 
 #include "internal.hpp"
 #include "ragged.hip.h"
@@ -1141,94 +1142,28 @@ struct LeanCols {
     const Fr* p[7];  // inputs of the primitive in order (+ the eq column for the generic object)
 };
 
-// deg-2 round sums with eq factored out (same contract as k_round_deg2<VECVEC, false>)
-template <int PRIM, bool VECVEC>
-__global__ void __launch_bounds__(SC_THREADS) k_round_deg2_lean(LeanCols cols, const Fr* __restrict__ eq, const Fr* __restrict__ gp,
-                                                                 uint64_t npairs_dense, VVArgs vv, FinishCtx fc) {
-    constexpr int NACC = VECVEC ? 3 : 2;
-    constexpr int NI = lean_n_in(PRIM);
-    Fr acc[3] = {fr_zero(), fr_zero(), fr_zero()};
-    if (VECVEC) {
-        for (uint32_t r = blockIdx.x * SC_THREADS + threadIdx.x; r < vv.nrows; r += gridDim.x * SC_THREADS) {
-            const uint32_t seg = (vv.off[r + 1] - vv.off[r]) >> 1;
-            acc[2] = fr_add(acc[2], fr_mul(fr_load(vv.row_coef + r), fr_sub(fr_one(), fr_load(vv.eq_prefix + seg))));
-        }
-    }
-    const uint64_t npairs = VECVEC ? (uint64_t)(vv.off[vv.nrows] >> 1) : npairs_dense;
-    for (uint64_t i = (uint64_t)blockIdx.x * SC_THREADS + threadIdx.x; i < npairs; i += (uint64_t)gridDim.x * SC_THREADS) {
-        Fr w;
-        if (VECVEC) {
-            const uint32_t cell0 = (uint32_t)(2 * i);
-            // 13 dependent loads of a full binary search per pair stall the few resident waves; the coarse table brackets the
-            // row to the rows that intersect one 256-cell block (one or two for long rows)
-            const uint32_t r = vv.coarse ? find_row_coarse(vv.off, vv.nrows, vv.coarse, cell0) : find_row(vv.off, vv.nrows, cell0);
-            w = fr_mul(fr_load(eq + ((cell0 - vv.off[r]) >> 1)), fr_load(vv.row_coef + r));
-        } else {
-            w = fr_load(eq + i);
-        }
-#pragma unroll 1
-        for (int h = 0; h < 2; h++) {
-            Fr v[NI];
-#pragma unroll
-            for (int q = 0; q < NI; q++) {
-                const Fr p1 = fr_load(cols.p[q] + 2 * i + 1);
-                v[q] = h ? fr_sub(fr_dbl(p1), fr_load(cols.p[q] + 2 * i)) : p1;
-            }
-            const Fr t = fr_mul(lean_gamma_eval<PRIM>(v, gp), w);
-            if (h == 0) acc[0] = fr_add(acc[0], t); else acc[1] = fr_add(acc[1], t);
-        }
-    }
-    block_reduce_finish<NACC>(acc, fc);
-}
-
-// The medium sparse rounds of a single-primitive layer (<= 2^14 pairs: latency-bound, one (pair, evaluation point) per thread as
-// k_round_deg2<true, true>, blockIdx.y = the point) with the re-associated gamma combination instead of prim_exec + one product per
-// output: PROJ_L1 7 + 2 multiplications on a thread's critical path instead of 9 + 3 + 2.
-template <int PRIM>
-__global__ void __launch_bounds__(SC_THREADS) k_round_deg2_lean_split(LeanCols cols, const Fr* __restrict__ eq, const Fr* __restrict__ gp, VVArgs vv,
-                                                                       FinishCtx fc) {
-    constexpr int NI = lean_n_in(PRIM);
-    Fr acc[3] = {fr_zero(), fr_zero(), fr_zero()};
-    if (blockIdx.y == 0) {
-        for (uint32_t r = blockIdx.x * SC_THREADS + threadIdx.x; r < vv.nrows; r += gridDim.x * SC_THREADS) {
-            const uint32_t seg = (vv.off[r + 1] - vv.off[r]) >> 1;
-            acc[2] = fr_add(acc[2], fr_mul(fr_load(vv.row_coef + r), fr_sub(fr_one(), fr_load(vv.eq_prefix + seg))));
-        }
-    }
-    const uint64_t npairs = (uint64_t)(vv.off[vv.nrows] >> 1);
-    const int h = blockIdx.y & 1;
-    for (uint64_t i = (uint64_t)blockIdx.x * SC_THREADS + threadIdx.x; i < npairs; i += (uint64_t)gridDim.x * SC_THREADS) {
-        const uint32_t cell0 = (uint32_t)(2 * i);
-        const uint32_t r = vv.coarse ? find_row_coarse(vv.off, vv.nrows, vv.coarse, cell0) : find_row(vv.off, vv.nrows, cell0);
-        const Fr w = fr_mul(fr_load(eq + ((cell0 - vv.off[r]) >> 1)), fr_load(vv.row_coef + r));
-        Fr v[NI];
-#pragma unroll
-        for (int q = 0; q < NI; q++) {
-            const Fr p1 = fr_load(cols.p[q] + 2 * i + 1);
-            v[q] = h ? fr_sub(fr_dbl(p1), fr_load(cols.p[q] + 2 * i)) : p1;
-        }
-        acc[h] = fr_add(acc[h], fr_mul(lean_gamma_eval<PRIM>(v, gp), w));
-    }
-    block_reduce_finish<3>(acc, fc);
-}
-
-// ---- the same large rounds in the 9 x 29-bit form (fr9.hip.h).  Inputs are loaded raw (the limbs of the stored value: domain
+// ---- deg-2 rounds of a single-primitive layer (lean_prim_of) with eq factored out, in the 9 x 29-bit form (fr9.hip.h): the same
+// contract as k_round_deg2<VECVEC, SPLIT>.  Inputs are loaded raw (the limbs of the stored value: domain
 // 256, S = 1 -- no conversion); every term of these layer functions is a product of exactly two inputs, so all of them land in
 // domain 251, the gamma powers are loaded in domain 261 (shifted loads: g x term stays in 251), the weight brings the
 // accumulators to domain 241 (VecVec: eq x coef) or 246 (dense), and ONE multiplication by 2^276 / 2^271 per thread at the end
-// returns to the stored form.  Same field values as k_round_deg2_lean, bit for bit (the sums are canonicalised before the block
-// reduction).  Bounds per line: L = limb bound, S = value / p (2^261 / p = 70.66).
-// Measured at config B (bench.py, ms per proof over the large launches, 9 x 29 vs 8 x 32): PROJ_L1 6.03 vs 6.25, PROJ_L2 5.10 vs
-// 5.22, PROJ_L3 4.65 vs 5.12, AFF_L1+BITCHECK 4.42 vs 5.13, AFF_L3 2.88 vs 3.26; gen-1 at 2^20 points: 353 vs 368 ms.
-// GM_LEAN_FR9=0 switches the form off (A/B measurements).
-__host__ __device__ constexpr bool lean9_has(int prim) {
-    return prim == FN_PROJ_L1 || prim == FN_PROJ_L2 || prim == FN_PROJ_L3 || prim == FN_AFF_L1 || prim == LEAN_AFF_L1_BC || prim == FN_AFF_L3 ||
-           prim == FN_AFF_L2 || prim == FN_PT_BIT_CHOICE || prim == FN_ADD_INVERSES || prim == FN_LOGUP_LAYER;
-}
+// returns to the stored form.  Same field values as the 8 x 32 form (lean_gamma_eval), bit for bit (the sums are canonicalised
+// before the block reduction).  Bounds per line: L = limb bound, S = value / p (2^261 / p = 70.66).
+// Measured at config B against the 8 x 32 form (since removed; bench.py, ms per proof over the large launches, 9 x 29 vs 8 x 32):
+// PROJ_L1 6.03 vs 6.25, PROJ_L2 5.10 vs 5.22, PROJ_L3 4.65 vs 5.12, AFF_L1+BITCHECK 4.42 vs 5.13, AFF_L3 2.88 vs 3.26; gen-1 at
+// 2^20 points: 353 vs 368 ms.
 // AFF_L2 and ADD_INVERSES have terms of degree one (a + b): those stay in domain 256, and their product term is brought there by
 // taking ONE factor from a shifted load (domain 261): (g v0) v1s is 261 + 256 - 261 = 256, times 261, minus 261 = 256.  Their
 // accumulators therefore sit five binary places higher than the others'.
 __host__ __device__ constexpr bool lean9_terms_256(int prim) { return prim == FN_AFF_L2 || prim == FN_ADD_INVERSES; }
+// eq x coef of the pair at cells (2 i, 2 i + 1) from raw loads: domain 251, S 1.02.  13 dependent loads of a full binary search
+// per pair stall the few resident waves; the coarse table brackets the row to the rows that intersect one 256-cell block (one or
+// two for long rows)
+__device__ __forceinline__ Fr9 vv_pair_weight9(VVArgs vv, const Fr* eq, uint64_t i) {
+    const uint32_t cell0 = (uint32_t)(2 * i);
+    const uint32_t r = vv.coarse ? find_row_coarse(vv.off, vv.nrows, vv.coarse, cell0) : find_row(vv.off, vv.nrows, cell0);
+    return fr9_mul(fr9_load_raw(eq + ((cell0 - vv.off[r]) >> 1)), fr9_load_raw(vv.row_coef + r));
+}
 // ld(q): input q at the evaluation point -- L 2^29, S <= 10, domain 256; loaded (and, at the second point, formed from the pair)
 // when the formula first needs it, in an order that keeps at most three inputs live: nine registers per value is what pushed the
 // six-input primitives to 256 VGPRs when all inputs were loaded up front.  Result: domain 251, L <= 5 2^29, S <= 30.
@@ -1340,62 +1275,9 @@ __device__ __forceinline__ auto lean_gamma_eval9(const LD& ld, const LDS& lds, c
     }
 }
 
-template <int PRIM, bool VECVEC>
-__global__ void __launch_bounds__(SC_THREADS, 3) k_round_deg2_lean9(LeanCols cols, const Fr* __restrict__ eq, const Fr* __restrict__ gp,
-                                                                  uint64_t npairs_dense, VVArgs vv, FinishCtx fc) {
-    constexpr int NACC = VECVEC ? 3 : 2;
-    Fr acc[3] = {fr_zero(), fr_zero(), fr_zero()};
-    if (VECVEC) {
-        for (uint32_t r = blockIdx.x * SC_THREADS + threadIdx.x; r < vv.nrows; r += gridDim.x * SC_THREADS) {
-            const uint32_t seg = (vv.off[r + 1] - vv.off[r]) >> 1;
-            acc[2] = fr_add(acc[2], fr_mul(fr_load(vv.row_coef + r), fr_sub(fr_one(), fr_load(vv.eq_prefix + seg))));
-        }
-    }
-    Fr9 a0 = fr9_zero(), a1 = fr9_zero();   // domain 241 (VecVec) / 246 (dense); normalised, S grows by <= 1.5 per pair
-    uint32_t it = 0;
-    const uint64_t npairs = VECVEC ? (uint64_t)(vv.off[vv.nrows] >> 1) : npairs_dense;
-    for (uint64_t i = (uint64_t)blockIdx.x * SC_THREADS + threadIdx.x; i < npairs; i += (uint64_t)gridDim.x * SC_THREADS, it++) {
-        Fr9 w;
-        if (VECVEC) {
-            const uint32_t cell0 = (uint32_t)(2 * i);
-            const uint32_t r = vv.coarse ? find_row_coarse(vv.off, vv.nrows, vv.coarse, cell0) : find_row(vv.off, vv.nrows, cell0);
-            w = fr9_mul(fr9_load_raw(eq + ((cell0 - vv.off[r]) >> 1)), fr9_load_raw(vv.row_coef + r));   // domain 251, S 1.02
-        } else {
-            w = fr9_load_raw(eq + i);                                                                      // domain 256, S 1
-        }
-#pragma unroll 1
-        for (int h = 0; h < 2; h++) {
-            auto ld = [&](int q) -> Fr9 {
-                const Fr9 p1 = fr9_load_raw(cols.p[q] + 2 * i + 1);
-                if (!h) return p1;
-                const Fr9 p0 = fr9_load_raw(cols.p[q] + 2 * i);
-                return fr9_norm(fr9_sub8(fr9_add(p1, p1), p0));         // 2 p1 - p0 + 8 p: S 10
-            };
-            auto lds = [&](int q) -> Fr9 {
-                const Fr9 p1 = fr9_load(cols.p[q] + 2 * i + 1);         // the limbs of 32 X: domain 261, S 32
-                if (!h) return p1;
-                const Fr9 p0 = fr9_load(cols.p[q] + 2 * i);
-                return fr9_norm(fr9_sub64(fr9_add(p1, p1), p0));        // 2 p1 - p0 + 64 p: S 128, top limb < 2^29.9
-            };
-            const Fr9 t = fr9_mul(lean_gamma_eval9<PRIM>(ld, lds, gp), w);   // L <= 5 2^29 x 2^29; S <= 37 x 1.02 / 70.66 + 1 = 1.6
-            if (h == 0) a0 = fr9_norm(fr9_add(a0, t)); else a1 = fr9_norm(fr9_add(a1, t));
-        }
-        if ((it & 15u) == 15u) {   // S <= 16 x 3 + 2: back below 2 (times one in domain 261 keeps the domain)
-            a0 = fr9_mul(a0, fr9_one());
-            a1 = fr9_mul(a1, fr9_one());
-        }
-    }
-    // back to the stored form: domain 241 / 246 times 2^276 / 2^271 (domain-free integers) = domain 256; S <= 50 / 70.66 + 1 < 2
-    // (terms in domain 256 -- lean9_terms_256 -- leave the accumulators five places higher: 2^271 / 2^266)
-    const Fr9 K = lean9_terms_256(PRIM) ? (VECVEC ? fr9_two271() : fr9_two266()) : (VECVEC ? fr9_two276() : fr9_two271());
-    acc[0] = fr9_to_raw(fr9_mul(a0, K));
-    acc[1] = fr9_to_raw(fr9_mul(a1, K));
-    block_reduce_finish<NACC>(acc, fc);
-}
-
-// The same round sums with every pair loaded ONCE: both evaluation points go through the layer function side by side (Fr9x2).
-// Twice the live values of k_round_deg2_lean9 (two waves per SIMD instead of three), in exchange for half the loads and two
-// interleaved multiplier chains.  Same field values, bit for bit.  GM_LEAN_X2=0 goes back to the one-point-at-a-time kernel.
+// Large rounds: every pair is loaded ONCE, both evaluation points go through the layer function side by side (Fr9x2): twice the
+// live values of one point at a time (two waves per SIMD instead of three), in exchange for half the loads and two interleaved
+// multiplier chains.
 template <int PRIM, bool VECVEC>
 __global__ void __launch_bounds__(SC_THREADS, 2) k_round_deg2_lean9x2(LeanCols cols, const Fr* __restrict__ eq, const Fr* __restrict__ gp,
                                                                     uint64_t npairs_dense, VVArgs vv, FinishCtx fc) {
@@ -1412,13 +1294,8 @@ __global__ void __launch_bounds__(SC_THREADS, 2) k_round_deg2_lean9x2(LeanCols c
     const uint64_t npairs = VECVEC ? (uint64_t)(vv.off[vv.nrows] >> 1) : npairs_dense;
     for (uint64_t i = (uint64_t)blockIdx.x * SC_THREADS + threadIdx.x; i < npairs; i += (uint64_t)gridDim.x * SC_THREADS, it++) {
         Fr9 w;
-        if (VECVEC) {
-            const uint32_t cell0 = (uint32_t)(2 * i);
-            const uint32_t r = vv.coarse ? find_row_coarse(vv.off, vv.nrows, vv.coarse, cell0) : find_row(vv.off, vv.nrows, cell0);
-            w = fr9_mul(fr9_load_raw(eq + ((cell0 - vv.off[r]) >> 1)), fr9_load_raw(vv.row_coef + r));   // domain 251, S 1.02
-        } else {
-            w = fr9_load_raw(eq + i);                                                                      // domain 256, S 1
-        }
+        if (VECVEC) w = vv_pair_weight9(vv, eq, i);   // domain 251, S 1.02
+        else w = fr9_load_raw(eq + i);                // domain 256, S 1
         auto ld = [&](int q) -> Fr9x2 {
             const Fr9 p0 = fr9_load_raw(cols.p[q] + 2 * i), p1 = fr9_load_raw(cols.p[q] + 2 * i + 1);
             return Fr9x2(p1, fr9_norm(fr9_sub8(fr9_add(p1, p1), p0)));      // p1 | 2 p1 - p0 + 8 p: S 10
@@ -1431,6 +1308,8 @@ __global__ void __launch_bounds__(SC_THREADS, 2) k_round_deg2_lean9x2(LeanCols c
         a = fr9_norm(fr9_add(a, t));
         if ((it & 15u) == 15u) a = fr9_mul(a, fr9_one());   // S <= 16 x 3 + 2: back below 2 (times one in domain 261 keeps the domain)
     }
+    // back to the stored form: domain 241 / 246 times 2^276 / 2^271 (domain-free integers) = domain 256; S <= 50 / 70.66 + 1 < 2
+    // (terms in domain 256 -- lean9_terms_256 -- leave the accumulators five places higher: 2^271 / 2^266)
     const Fr9 K = lean9_terms_256(PRIM) ? (VECVEC ? fr9_two271() : fr9_two266()) : (VECVEC ? fr9_two276() : fr9_two271());
     a = fr9_mul(a, K);
     acc[0] = fr9_to_raw(a.a);
@@ -1440,7 +1319,7 @@ __global__ void __launch_bounds__(SC_THREADS, 2) k_round_deg2_lean9x2(LeanCols c
 
 // The medium sparse rounds (<= 2^14 pairs: latency-bound) of a single-primitive layer in the same form: one (pair, evaluation point) per
 // thread, blockIdx.y = the point; the tail weight (a loop over the ROWS) runs in workgroup row y = 2 of its own instead of ahead of the
-// pairs in row 0, whose threads were the launch's critical path.  Same sums as k_round_deg2_lean_split, bit for bit.
+// pairs in row 0, whose threads were the launch's critical path.  Same sums as k_round_deg2<true, true>, bit for bit.
 template <int PRIM>
 __global__ void __launch_bounds__(SC_THREADS) k_round_deg2_lean9_split(LeanCols cols, const Fr* __restrict__ eq, const Fr* __restrict__ gp,
                                                                         VVArgs vv, FinishCtx fc) {
@@ -1458,9 +1337,7 @@ __global__ void __launch_bounds__(SC_THREADS) k_round_deg2_lean9_split(LeanCols 
     uint32_t it = 0;
     const uint64_t npairs = (uint64_t)(vv.off[vv.nrows] >> 1);
     for (uint64_t i = (uint64_t)blockIdx.x * SC_THREADS + threadIdx.x; i < npairs; i += (uint64_t)gridDim.x * SC_THREADS, it++) {
-        const uint32_t cell0 = (uint32_t)(2 * i);
-        const uint32_t r = vv.coarse ? find_row_coarse(vv.off, vv.nrows, vv.coarse, cell0) : find_row(vv.off, vv.nrows, cell0);
-        const Fr9 w = fr9_mul(fr9_load_raw(eq + ((cell0 - vv.off[r]) >> 1)), fr9_load_raw(vv.row_coef + r));   // domain 251, S 1.02
+        const Fr9 w = vv_pair_weight9(vv, eq, i);   // domain 251, S 1.02
         auto ld = [&](int q) -> Fr9 {
             const Fr9 p1 = fr9_load_raw(cols.p[q] + 2 * i + 1);
             if (!h) return p1;
@@ -2492,87 +2369,29 @@ static int lean_prim_of(const SegPlan& sp) {
     return 0;
 }
 
-template <bool VECVEC>
-static int32_t launch_deg2_lean(int prim, dim3 grid, hipStream_t s, const LeanCols& lc, const Fr* eq, const Fr* gp, uint64_t npairs,
-                                const VVArgs& va, const FinishCtx& fc) {
-#define GM_LEAN_CASE(P)                                                                                                  \
-    case P: hipLaunchKernelGGL((k_round_deg2_lean<P, VECVEC>), grid, dim3(SC_THREADS), 0, s, lc, eq, gp, npairs, va, fc); break;
-    static const bool use9 = [] { const char* e = getenv("GM_LEAN_FR9"); return !(e && e[0] == '0'); }();
-    static const bool usex2 = [] { const char* e = getenv("GM_LEAN_X2"); return !(e && e[0] == '0'); }();
-    if (use9 && usex2 && lean9_has(prim)) {
-#define GM_LEAN9X2_CASE(P)                                                                                               \
-    case P: hipLaunchKernelGGL((k_round_deg2_lean9x2<P, VECVEC>), grid, dim3(SC_THREADS), 0, s, lc, eq, gp, npairs, va, fc); break;
-        switch (prim) {
-            GM_LEAN9X2_CASE(FN_AFF_L1) GM_LEAN9X2_CASE(FN_AFF_L3) GM_LEAN9X2_CASE(FN_PROJ_L1) GM_LEAN9X2_CASE(FN_PROJ_L2)
-            GM_LEAN9X2_CASE(FN_PROJ_L3) GM_LEAN9X2_CASE(LEAN_AFF_L1_BC) GM_LEAN9X2_CASE(FN_AFF_L2) GM_LEAN9X2_CASE(FN_PT_BIT_CHOICE)
-            GM_LEAN9X2_CASE(FN_ADD_INVERSES) GM_LEAN9X2_CASE(FN_LOGUP_LAYER)
-        }
-#undef GM_LEAN9X2_CASE
-        GM_LAUNCH_CHECK();
-        return GM_OK;
-    }
-    if (use9 && lean9_has(prim)) {
-#define GM_LEAN9_CASE(P)                                                                                                 \
-    case P: hipLaunchKernelGGL((k_round_deg2_lean9<P, VECVEC>), grid, dim3(SC_THREADS), 0, s, lc, eq, gp, npairs, va, fc); break;
-        switch (prim) {
-            GM_LEAN9_CASE(FN_AFF_L1) GM_LEAN9_CASE(FN_AFF_L3) GM_LEAN9_CASE(FN_PROJ_L1) GM_LEAN9_CASE(FN_PROJ_L2)
-            GM_LEAN9_CASE(FN_PROJ_L3) GM_LEAN9_CASE(LEAN_AFF_L1_BC) GM_LEAN9_CASE(FN_AFF_L2) GM_LEAN9_CASE(FN_PT_BIT_CHOICE)
-            GM_LEAN9_CASE(FN_ADD_INVERSES) GM_LEAN9_CASE(FN_LOGUP_LAYER)
-        }
-#undef GM_LEAN9_CASE
-        GM_LAUNCH_CHECK();
-        return GM_OK;
-    }
+// The primitives with lean round kernels (lean_prim_of) and the kernels each of them can reach:
+//   k_round_deg2_lean9x2<P, dense|VecVec>  every one: large deg-2 rounds (launch_round_deg2)
+//   k_round_deg2_lean9_split<P>            lean_has_split(P): medium VecVec rounds (launch_round_deg2); the others run
+//                                          k_round_deg2<true, true> there
+//   k_round_generic3_lean<P>               lean_has_generic3(P): large rounds of a deg-3 ScDense object (kind 0)
+constexpr bool lean_has_split(int prim) { return prim != FN_PT_BIT_CHOICE && prim != FN_ADD_INVERSES && prim != FN_LOGUP_LAYER; }
+constexpr bool lean_has_generic3(int prim) { return prim != LEAN_AFF_L1_BC; }
+// f(std::integral_constant<int, prim>()); false when prim has no lean kernels
+template <typename F>
+static bool with_lean_prim(int prim, F&& f) {
     switch (prim) {
-        GM_LEAN_CASE(FN_AFF_L1) GM_LEAN_CASE(FN_AFF_L2) GM_LEAN_CASE(FN_AFF_L3) GM_LEAN_CASE(FN_PROJ_L1)
-        GM_LEAN_CASE(FN_PROJ_L2) GM_LEAN_CASE(FN_PROJ_L3) GM_LEAN_CASE(FN_PT_BIT_CHOICE) GM_LEAN_CASE(LEAN_AFF_L1_BC)
-        GM_LEAN_CASE(FN_ADD_INVERSES) GM_LEAN_CASE(FN_LOGUP_LAYER)
-        default: return set_err(GM_ERR_STATE, "no lean kernel for primitive %d", prim);
-    }
-#undef GM_LEAN_CASE
-    GM_LAUNCH_CHECK();
-    return GM_OK;
-}
-
-static bool launch_deg2_lean_split(int prim, dim3 grid, hipStream_t s, const LeanCols& lc, const Fr* eq, const Fr* gp, const VVArgs& va,
-                                   const FinishCtx& fc) {
-    static const bool off = [] { const char* e = getenv("GM_LEAN_SPLIT"); return e && e[0] == '0'; }();
-    if (off) return false;
-    static const bool form9 = [] { const char* e = getenv("GM_LEAN_SPLIT9"); return !(e && e[0] == '0'); }();   // A/B: the 8 x 32 form
-    if (form9) {
-        const dim3 g3(grid.x, 3);   // row 2: the tail weight
-#define GM_LS9_CASE(P) \
-    case P: hipLaunchKernelGGL((k_round_deg2_lean9_split<P>), g3, dim3(SC_THREADS), 0, s, lc, eq, gp, va, fc); return true;
-        switch (prim) {
-            GM_LS9_CASE(FN_AFF_L1) GM_LS9_CASE(FN_AFF_L2) GM_LS9_CASE(FN_AFF_L3) GM_LS9_CASE(FN_PROJ_L1) GM_LS9_CASE(FN_PROJ_L2)
-            GM_LS9_CASE(FN_PROJ_L3) GM_LS9_CASE(LEAN_AFF_L1_BC)
-            default: break;
-        }
-#undef GM_LS9_CASE
-    }
-#define GM_LS_CASE(P) \
-    case P: hipLaunchKernelGGL((k_round_deg2_lean_split<P>), grid, dim3(SC_THREADS), 0, s, lc, eq, gp, va, fc); return true;
-    switch (prim) {
-        GM_LS_CASE(FN_AFF_L1) GM_LS_CASE(FN_AFF_L2) GM_LS_CASE(FN_AFF_L3) GM_LS_CASE(FN_PROJ_L1) GM_LS_CASE(FN_PROJ_L2) GM_LS_CASE(FN_PROJ_L3)
-        GM_LS_CASE(LEAN_AFF_L1_BC)
+        case FN_AFF_L1: f(std::integral_constant<int, FN_AFF_L1>()); return true;
+        case FN_AFF_L2: f(std::integral_constant<int, FN_AFF_L2>()); return true;
+        case FN_AFF_L3: f(std::integral_constant<int, FN_AFF_L3>()); return true;
+        case FN_PROJ_L1: f(std::integral_constant<int, FN_PROJ_L1>()); return true;
+        case FN_PROJ_L2: f(std::integral_constant<int, FN_PROJ_L2>()); return true;
+        case FN_PROJ_L3: f(std::integral_constant<int, FN_PROJ_L3>()); return true;
+        case FN_PT_BIT_CHOICE: f(std::integral_constant<int, FN_PT_BIT_CHOICE>()); return true;
+        case LEAN_AFF_L1_BC: f(std::integral_constant<int, LEAN_AFF_L1_BC>()); return true;
+        case FN_ADD_INVERSES: f(std::integral_constant<int, FN_ADD_INVERSES>()); return true;
+        case FN_LOGUP_LAYER: f(std::integral_constant<int, FN_LOGUP_LAYER>()); return true;
         default: return false;
     }
-#undef GM_LS_CASE
-}
-
-static int32_t launch_generic3_lean(int prim, dim3 grid, hipStream_t s, const LeanCols& lc, const Fr* gp, uint64_t npairs,
-                                    const FinishCtx& fc) {
-#define GM_LEAN_CASE(P)                                                                                                  \
-    case P: hipLaunchKernelGGL((k_round_generic3_lean<P>), grid, dim3(SC_THREADS), 0, s, lc, gp, npairs, fc); break;
-    switch (prim) {
-        GM_LEAN_CASE(FN_AFF_L1) GM_LEAN_CASE(FN_AFF_L2) GM_LEAN_CASE(FN_AFF_L3) GM_LEAN_CASE(FN_PROJ_L1)
-        GM_LEAN_CASE(FN_PROJ_L2) GM_LEAN_CASE(FN_PROJ_L3) GM_LEAN_CASE(FN_PT_BIT_CHOICE)
-        GM_LEAN_CASE(FN_ADD_INVERSES) GM_LEAN_CASE(FN_LOGUP_LAYER)
-        default: return set_err(GM_ERR_STATE, "no lean kernel for primitive %d", prim);
-    }
-#undef GM_LEAN_CASE
-    GM_LAUNCH_CHECK();
-    return GM_OK;
 }
 
 // ---- profiler (gm_sc_profile): the large round kernels timed with HIP events on their launch stream --------------------
@@ -2609,7 +2428,8 @@ static ScProf& sc_prof() {
     return p;
 }
 static const char* sc_class_name(int cls) {
-    // cls = prim * 4 + variant; variant 0: k_round_deg2_lean dense, 1: k_round_deg2_lean VecVec, 2: k_round_generic3_lean, 3: k_round_prod3_lean
+    // cls = prim * 4 + variant; variant 0: k_round_deg2_lean9x2 dense, 1: k_round_deg2_lean9x2 VecVec (both in rows named
+    // k_round_deg2_lean<>), 2: k_round_generic3_lean, 3: k_round_prod3_lean
     static thread_local char buf[64];
     const int prim = cls >> 2, var = cls & 3;
     const char* pn = prim == FN_AFF_L1 ? "AFF_L1" : prim == FN_AFF_L2 ? "AFF_L2" : prim == FN_AFF_L3 ? "AFF_L3" : prim == FN_PROJ_L1 ? "PROJ_L1"
@@ -2656,6 +2476,57 @@ static inline void prof_small_round(double bytes) {
 static inline void prof_fold(double bytes) {
     ScProf& p = sc_prof();
     if (p.mode >= 2) { p.fold_bytes += bytes; p.folds += 1; }
+}
+
+// The round kernel of one deg-2 round (ScDenseDeg2, ScVecVecDeg2) over the k columns `cols`: small rounds in split mode (the lean
+// split kernel for a single-primitive VecVec layer that has one, else k_round_deg2<, true>), large rounds in the lean kernel of a
+// single-primitive layer, else k_round_deg2<, false>.  vv: the VecVec arguments, or nullptr for dense columns.  npairs: the pair
+// count (VecVec: cb / 2 from the capacity bound cb of the cells; the exact count lives on the device, off[nrows]).
+static int32_t launch_round_deg2(hipStream_t s, const SegPlan& sp, const Fr* const* cols, int k, const Fr* eq, const Fr* gp,
+                                 uint64_t npairs, const VVArgs* vv, const FinishCtx& fc) {
+    const VVArgs none{nullptr, 0, nullptr, nullptr, nullptr};
+    const VVArgs& va = vv ? *vv : none;
+    const uint64_t npairs_dense = vv ? 0 : npairs;
+    // VecVec: the grid from the capacity bound, and at least one thread per row (the tail-weight loop runs over rows)
+    const uint64_t bound_pairs = vv ? npairs + 1 : npairs;
+    const bool split = bound_pairs <= SC_SPLIT_MAX_PAIRS;
+    const dim3 grid = round_grid(vv && vv->nrows > bound_pairs ? vv->nrows : bound_pairs, split ? 2 * sp.nseg : 1);
+    const int lean = k <= 6 ? lean_prim_of(sp) : 0;
+    LeanCols lc;
+    ColPtrs cp;
+    for (int i = 0; i < k; i++) {
+        if (i < 7) lc.p[i] = cols[i];
+        cp.p[i] = cols[i];
+    }
+    if (lean && !split) {
+        const int pi = prof_begin(s, lean * 4 + (vv ? 1 : 0), k, npairs, vv ? vv->off + vv->nrows : nullptr,
+                                  2 * lean_eval_muls(lean) + (vv ? 3 : 2));
+        const bool ok = with_lean_prim(lean, [&](auto P) {
+            if (vv)
+                hipLaunchKernelGGL((k_round_deg2_lean9x2<decltype(P)::value, true>), grid, dim3(SC_THREADS), 0, s, lc, eq, gp,
+                                   npairs_dense, va, fc);
+            else
+                hipLaunchKernelGGL((k_round_deg2_lean9x2<decltype(P)::value, false>), grid, dim3(SC_THREADS), 0, s, lc, eq, gp,
+                                   npairs_dense, va, fc);
+        });
+        prof_end(s, pi);
+        if (!ok) return set_err(GM_ERR_STATE, "no lean kernel for primitive %d", lean);
+    } else if (split && vv && lean && lean_has_split(lean)) {
+        with_lean_prim(lean, [&](auto P) {   // row y = 2: the tail weight
+            if constexpr (lean_has_split(decltype(P)::value))
+                hipLaunchKernelGGL((k_round_deg2_lean9_split<decltype(P)::value>), dim3(grid.x, 3), dim3(SC_THREADS), 0, s, lc, eq, gp,
+                                   va, fc);
+        });
+    } else if (split) {
+        if (vv) hipLaunchKernelGGL((k_round_deg2<true, true>), grid, dim3(SC_THREADS), 0, s, sp, cp, eq, gp, npairs_dense, va, fc);
+        else hipLaunchKernelGGL((k_round_deg2<false, true>), grid, dim3(SC_THREADS), 0, s, sp, cp, eq, gp, npairs_dense, va, fc);
+    } else {
+        if (vv) hipLaunchKernelGGL((k_round_deg2<true, false>), grid, dim3(SC_THREADS), 0, s, sp, cp, eq, gp, npairs_dense, va, fc);
+        else hipLaunchKernelGGL((k_round_deg2<false, false>), grid, dim3(SC_THREADS), 0, s, sp, cp, eq, gp, npairs_dense, va, fc);
+    }
+    GM_LAUNCH_CHECK();
+    if (!lean || split) prof_small_round(64.0 * k * (double)npairs);
+    return GM_OK;
 }
 
 // ---- columns with ping-pong fold buffers --------------------------------------------------------
@@ -2826,13 +2697,17 @@ struct ScDense : gm_sc {
             const int pi = prof_begin(stream, 3, 3, npairs, nullptr, 3 * 2);
             hipLaunchKernelGGL(k_round_prod3_lean, grid, dim3(SC_THREADS), 0, stream, lc, npairs, fc);
             prof_end(stream, pi);
-        } else if (lean && lean != LEAN_AFF_L1_BC) {
+        } else if (lean && lean_has_generic3(lean)) {
             LeanCols lc;
             for (int i = 0; i < cols.k; i++) lc.p[i] = cur_cols[i];
             const int pi = prof_begin(stream, lean * 4 + 2, cols.k, npairs, nullptr, 3 * (lean_eval_muls(lean) + 1));
-            int32_t rc = launch_generic3_lean(lean, grid, stream, lc, d_gamma.fr(), npairs, fc);
+            const bool ok = with_lean_prim(lean, [&](auto P) {
+                if constexpr (lean_has_generic3(decltype(P)::value))
+                    hipLaunchKernelGGL((k_round_generic3_lean<decltype(P)::value>), grid, dim3(SC_THREADS), 0, stream, lc, d_gamma.fr(),
+                                       npairs, fc);
+            });
             prof_end(stream, pi);
-            if (rc) return rc;
+            if (!ok) return set_err(GM_ERR_STATE, "no lean kernel for primitive %d", lean);
         } else if (D == 3 && split)
             hipLaunchKernelGGL((k_round_generic<3, true>), grid, dim3(SC_THREADS), 0, stream, kind, sp, cp, cols.k,
                                d_gamma.fr(), npairs, fc);
@@ -3015,15 +2890,10 @@ struct ScDenseDeg2 : gm_sc {
         const Fr* eq_cur = eq_at(num_vars - 1 - round_idx, glob_off >> 1);
         ColPtrs cp;
         for (int i = 0; i < cols.k; i++) cp.p[i] = cols.cur[i];
-        const bool split = npairs <= SC_SPLIT_MAX_PAIRS;
-        const dim3 grid = round_grid(npairs, split ? 2 * sp.nseg : 1);
-        const VVArgs none{nullptr, 0, nullptr, nullptr, nullptr};
-        const int lean = (!split && cols.k <= 6) ? lean_prim_of(sp) : 0;
-        // results of pre-enqueued kernels land in the pinned staging: it must be this object's alone for the duration
-        static const bool pipe_large = [] { const char* e = getenv("GM_SC_PIPE_LARGE_DENSE"); return !(e && e[0] == '0'); }();   // A/B switch
         const bool devx = RoundScratch::dev_exchange(sh);
         // sharded with the round sums meeting on the host: the device side of a round is the unsharded one
-        if ((split || pipe_large) && !devx && pipeline_enabled() && (rs.own_pinned || pinned_exclusive() || k_enq > round_idx))
+        // results of pre-enqueued kernels land in the pinned staging: it must be this object's alone for the duration
+        if (!devx && pipeline_enabled() && (rs.own_pinned || pinned_exclusive() || k_enq > round_idx))
             return unipoly_pipelined(coeffs, npairs, eq_cur, cp);
         FinishCtx fc0;
         if (devx) {
@@ -3032,27 +2902,14 @@ struct ScDenseDeg2 : gm_sc {
         } else {
             fc0 = rs.ctx();
         }
-        if (lean) {
-            LeanCols lc;
-            for (int i = 0; i < cols.k; i++) lc.p[i] = cols.cur[i];
-            const int pi = prof_begin(stream, lean * 4 + 0, cols.k, npairs, nullptr, 2 * lean_eval_muls(lean) + 2);
-            int32_t rc = launch_deg2_lean<false>(lean, grid, stream, lc, eq_cur, d_gamma.fr(), npairs, none, fc0);
-            prof_end(stream, pi);
-            if (rc) return rc;
-        } else if (split)
-            hipLaunchKernelGGL((k_round_deg2<false, true>), grid, dim3(SC_THREADS), 0, stream, sp, cp,
-                               eq_cur, d_gamma.fr(), npairs, none, fc0);
-        else
-            hipLaunchKernelGGL((k_round_deg2<false, false>), grid, dim3(SC_THREADS), 0, stream, sp, cp,
-                               eq_cur, d_gamma.fr(), npairs, none, fc0);
-        GM_LAUNCH_CHECK();
-        if (!lean) prof_small_round(64.0 * cols.k * (double)npairs);
+        int32_t rc = launch_round_deg2(stream, sp, cols.cur.data(), cols.k, eq_cur, d_gamma.fr(), npairs, nullptr, fc0);
+        if (rc) return rc;
         if (devx) {
             int32_t rc = rs.exchange(sh, 2, stream);
             if (rc) return rc;
         }
         Fr acc[4];
-        int32_t rc = rs.finish(2, stream, acc);
+        rc = rs.finish(2, stream, acc);
         if (rc) return rc;
         if (sh.comm && !devx) {
             rc = shard_sum_fr(sh, acc, 2);
@@ -3081,26 +2938,10 @@ struct ScDenseDeg2 : gm_sc {
     // the generic kernel for large ones (large rounds are pre-enqueued too: the fold and the next round kernel are then already
     // in the stream when the challenge arrives, ~10 us of launch latency per round)
     int32_t launch_small_round(const ColPtrs& cp, const Fr* eq, uint64_t npairs, uint32_t round) {
-        const bool split = npairs <= SC_SPLIT_MAX_PAIRS;
-        const dim3 grid = round_grid(npairs, split ? 2 * sp.nseg : 1);
-        const VVArgs none{nullptr, 0, nullptr, nullptr, nullptr};
-        const int lean = (!split && cols.k <= 6) ? lean_prim_of(sp) : 0;
         const FinishCtx fc = rs.ctx();
-        if (lean) {
-            LeanCols lc;
-            for (int i = 0; i < cols.k; i++) lc.p[i] = cp.p[i];
-            const int pi = prof_begin(stream, lean * 4 + 0, cols.k, npairs, nullptr, 2 * lean_eval_muls(lean) + 2);
-            int32_t rc = launch_deg2_lean<false>(lean, grid, stream, lc, eq, d_gamma.fr(), npairs, none, fc);
-            prof_end(stream, pi);
-            if (rc) return rc;
-        } else if (split) {
-            hipLaunchKernelGGL((k_round_deg2<false, true>), grid, dim3(SC_THREADS), 0, stream, sp, cp, eq, d_gamma.fr(), npairs, none, fc);
-        } else {
-            hipLaunchKernelGGL((k_round_deg2<false, false>), grid, dim3(SC_THREADS), 0, stream, sp, cp, eq, d_gamma.fr(), npairs, none, fc);
-        }
-        GM_LAUNCH_CHECK();
+        int32_t rc = launch_round_deg2(stream, sp, cp.p, cols.k, eq, d_gamma.fr(), npairs, nullptr, fc);
+        if (rc) return rc;
         k_seq[round & 63] = fc.seq;
-        if (!lean) prof_small_round(64.0 * cols.k * (double)npairs);
         return GM_OK;
     }
     // ---- persistent stage (see k_stage): rounds [tail_r0, num_vars) run inside one launch
@@ -3678,15 +3519,7 @@ struct ScVecVecDeg2 : gm_sc {
         const size_t lvl = eq_level_len.size() - 1 - ab;
         const Fr* eq_row = d_eq_seq.fr() + eq_level_off[lvl];
         const Fr* eq_pre = d_prefix.fr() + eq_level_off[lvl] + lvl;  // level l has len+1 prefix entries
-        ColPtrs cp;
-        for (int i = 0; i < k; i++) cp.p[i] = cols_now[i];
-        // grid from the capacity bound: the exact cell count lives on the device (off[nrows])
-        const uint64_t bound_pairs = cb / 2 + 1;
-        const bool split = bound_pairs <= SC_SPLIT_MAX_PAIRS;
-        const uint64_t gx = bound_pairs > nrows ? bound_pairs : nrows;  // the tail-weight loop runs over rows
-        const dim3 grid = round_grid(gx, split ? 2 * sp.nseg : 1);
         const VVArgs va{off, nrows, d_row_coef.fr() + row_base, eq_pre, coarse_for(off)};
-        const int lean = (!split && k <= 6) ? lean_prim_of(sp) : 0;
         FinishCtx fc;
         if (RoundScratch::dev_exchange(sh)) {
             int32_t rc = rs.ctx_dev(sh, &fc);
@@ -3694,28 +3527,9 @@ struct ScVecVecDeg2 : gm_sc {
         } else {
             fc = rs.ctx();
         }
-        if (lean) {
-            LeanCols lc;
-            for (int i = 0; i < k; i++) lc.p[i] = cols_now[i];
-            const int pi = prof_begin(stream, lean * 4 + 1, k, cb / 2, off + nrows, 2 * lean_eval_muls(lean) + 3);
-            int32_t rc = launch_deg2_lean<true>(lean, grid, stream, lc, eq_row, d_gamma.fr(), (uint64_t)0, va, fc);
-            prof_end(stream, pi);
-            if (rc) return rc;
-        } else if (split) {
-            // single-primitive layers: the lean split kernel (two workgroup rows, one per evaluation point)
-            const int lean_s = k <= 6 ? lean_prim_of(sp) : 0;
-            LeanCols lc;
-            for (int i = 0; i < k && i < 7; i++) lc.p[i] = cols_now[i];
-            if (!(lean_s && launch_deg2_lean_split(lean_s, dim3(grid.x, 2), stream, lc, eq_row, d_gamma.fr(), va, fc)))
-                hipLaunchKernelGGL((k_round_deg2<true, true>), grid, dim3(SC_THREADS), 0, stream, sp, cp, eq_row, d_gamma.fr(),
-                                   (uint64_t)0, va, fc);
-        }
-        else
-            hipLaunchKernelGGL((k_round_deg2<true, false>), grid, dim3(SC_THREADS), 0, stream, sp, cp, eq_row, d_gamma.fr(),
-                               (uint64_t)0, va, fc);
-        GM_LAUNCH_CHECK();
+        int32_t rc = launch_round_deg2(stream, sp, cols_now, k, eq_row, d_gamma.fr(), cb / 2, &va, fc);
+        if (rc) return rc;
         k_seq[ab & 63] = fc.seq;
-        if (!lean) prof_small_round(64.0 * k * (double)(cb / 2));   // capacity bound of the cells (exact count lives on the device)
         return GM_OK;
     }
     ~ScVecVecDeg2() override {

@@ -1,5 +1,6 @@
 """Integer model of the 9 x 29-bit field form (gkr_msm_amd/csrc/fr9.hip.h) and of every formula the kernels evaluate in it
-(msm.hip: aff_add9 / proj_add9; sumcheck.hip: lean_gamma_eval9 + the accumulate / finish steps of k_round_deg2_lean9).
+(msm.hip: aff_add9 / proj_add9; sumcheck.hip: lean_gamma_eval9 + the accumulate / finish steps of k_round_deg2_lean9x2 and
+k_round_deg2_lean9_split, one evaluation point at a time).
 
 The device code relies on static bounds: a column of the product never exceeds 64 bits, a limb-wise difference never goes below
 zero, a limb-wise sum never wraps 32 bits, a value handed to fr9_store is below 33 p.  The model restates the routines limb for
@@ -318,8 +319,9 @@ TERMS_256 = ("AFF_L2", "ADD_INVERSES")   # their terms stay in domain 256: the a
 
 
 def test_large_round_kernels_in_the_raw_form():
-    """one thread of k_round_deg2_lean9: 40 pairs (so the every-16-pairs scale reduction runs twice), both evaluation points, the
-    VecVec weight (eq x coef) and the dense one (eq), finish by 2^276 / 2^271 and the canonical store"""
+    """one thread of k_round_deg2_lean9x2 (each of its two components; k_round_deg2_lean9_split computes one): 40 pairs (so the
+    every-16-pairs scale reduction runs twice), both evaluation points, the VecVec weight (eq x coef) and the dense one (eq),
+    finish by 2^276 / 2^271 and the canonical store"""
     vals = stored_values(4, 3)
     rng = random.Random(4)
     for prim, ni in N_IN.items():

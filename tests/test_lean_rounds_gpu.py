@@ -1,10 +1,9 @@
 """The large-round lean kernels of csrc/sumcheck.hip against the Python oracle, at small sizes and at the edges of their lazy bounds.
 
 lean_prim_of is consulted only for rounds above SC_SPLIT_MAX_PAIRS pairs (2^14), so the ordinary small tests never reach
-k_round_deg2_lean9x2 / _lean9 / _lean, k_round_deg2_lean9_split / _lean_split, k_round_generic3_lean or k_round_prod3_lean.  The
-dispatch reads GM_SC_SPLIT_MAX_LOG (and the A/B switches GM_LEAN_X2, GM_LEAN_FR9, GM_LEAN_SPLIT9) once per process, so the checks
-run in child pytest processes with a small threshold and GM_SC_NO_TAIL=1 (the persistent k_stage would otherwise absorb the
-object); the child cases skip when those variables are absent.  Every child case asserts, through gm_sc_profile, which lean kernel
+k_round_deg2_lean9x2, k_round_deg2_lean9_split, k_round_generic3_lean or k_round_prod3_lean.  The dispatch reads
+GM_SC_SPLIT_MAX_LOG once per process, so the checks run in child pytest processes with a small threshold and GM_SC_NO_TAIL=1
+(the persistent k_stage would otherwise absorb the object); the child cases skip when those variables are absent.  Every child case asserts, through gm_sc_profile, which lean kernel
 rows ran with how many pairs, and that no k_stage was launched.
 
 The lazy 9 x 29-bit form is argued per operation in comments ("S <= 10", "S grows by <= 1.5 per pair"); the operands here are
@@ -291,9 +290,9 @@ SPLIT_CASES = [("proj_l1", 6, 1, "full"), ("aff_l1_bc", 6, 2, "rows"), ("aff_l2"
 
 @pytest.mark.parametrize("name,row_log,col_log,mode", SPLIT_CASES)
 def test_child_vecvec_lean_then_split(name, row_log, col_log, mode):
-    """one object whose large sparse rounds run k_round_deg2_lean9x2<,true> (or its A/B forms) and whose last sparse rounds run
-    k_round_deg2_lean9_split (GM_LEAN_SPLIT9=0: k_round_deg2_lean_split); ADD_INVERSES, LOGUP_LAYER and PT_BIT_CHOICE have no
-    split form and run k_round_deg2<true, true> there"""
+    """one object whose large sparse rounds run k_round_deg2_lean9x2<,true> and whose last sparse rounds run
+    k_round_deg2_lean9_split; ADD_INVERSES, LOGUP_LAYER and PT_BIT_CHOICE have no split form and run k_round_deg2<true, true>
+    there"""
     lg = need_group("split")
     rng = F.SplitMix64(0x5917 + row_log * 10 + col_log + len(name))
     py, gpu_vv = vv_operands(rng, name, row_log, col_log, mode)
@@ -305,18 +304,16 @@ def test_child_vecvec_lean_then_split(name, row_log, col_log, mode):
 
 
 GROUP_CASES = {"lean": len(DENSE_CASES) + len(EDGE_CASES) + len(GENERIC_CASES) + len(VV_CASES), "split": len(SPLIT_CASES)}
-FORMS = [  # (id, A/B switches, group, GM_SC_SPLIT_MAX_LOG)
-    ("default", {}, "lean", 0), ("x2_off", {"GM_LEAN_X2": "0"}, "lean", 0), ("fr9_off", {"GM_LEAN_FR9": "0"}, "lean", 0),
-    ("split_default", {}, "split", 3), ("split9_off", {"GM_LEAN_SPLIT9": "0"}, "split", 3)]
+FORMS = [("default", "lean", 0), ("split_default", "split", 3)]   # (id, group, GM_SC_SPLIT_MAX_LOG)
 
 
-@pytest.mark.parametrize("form,switches,group,lg", FORMS, ids=[f[0] for f in FORMS])
-def test_lean_kernels_against_oracle(form, switches, group, lg):
-    """one child process per dispatch setting (the switches are read once per process); the child must pass every case of its
-    group: a skip there means a case did not run"""
+@pytest.mark.parametrize("form,group,lg", FORMS, ids=[f[0] for f in FORMS])
+def test_lean_kernels_against_oracle(form, group, lg):
+    """one child process per split threshold (read once per process); the child must pass every case of its group: a skip there
+    means a case did not run"""
     if "GM_LEAN_GROUP" in os.environ:
         pytest.skip("already in a child")
-    env = dict(os.environ, GM_SC_SPLIT_MAX_LOG=str(lg), GM_SC_NO_TAIL="1", GM_LEAN_GROUP=group, **switches)
+    env = dict(os.environ, GM_SC_SPLIT_MAX_LOG=str(lg), GM_SC_NO_TAIL="1", GM_LEAN_GROUP=group)
     out = subprocess.run([sys.executable, "-m", "pytest", os.path.abspath(__file__), "-q", "-x", "-k", "test_child_"], env=env,
                          cwd=ROOT, capture_output=True, text=True, timeout=600)
     if out.returncode < 0 or out.returncode in (134, 139):   # the device faulted: start nothing more on it
