@@ -163,7 +163,7 @@ Fr eq_sum_host(const Fr* pt, uint32_t n, uint64_t k) {
 }
 
 // ------------------------------------------------------------------------------------------ wait bound
-// Kernels that wait on the device for the host's next challenge (k_fold_gate, k_tail_rounds) and the host loops that wait for
+// Kernels that wait on the device for the host's next challenge (k_fold_gate, k_stage) and the host loops that wait for
 // their results give up after this long (gm_set_wait_timeout_ms; default 20 s).  Device side: wall_clock64() ticks (100 MHz).
 // (wait_timeout_ms / wait_timeout_ticks / wait_timeout_host: internal.hpp -- the shared-memory communicator waits by the same bound)
 
@@ -1767,6 +1767,8 @@ struct RoundScratch {
     ~RoundScratch() {
         if (h_result && own_pinned) (void)hipHostFree(h_result);
     }
+    // the pinned staging is this object's alone: kernels enqueued ahead may report through it
+    bool pinned_ours() const { return own_pinned || pinned_exclusive(); }
     static uint32_t& seq_counter() {
         static thread_local uint32_t c = 0;
         return c;
@@ -1797,6 +1799,12 @@ struct RoundScratch {
         fc->raw = 0;   // k_sum_ranks adds field elements
         return GM_OK;
     }
+    // the report of a round kernel: this rank's device slot when the sharded sums meet on the device, else the pinned staging
+    int32_t round_ctx(const Shard& sh, FinishCtx* fc) {
+        if (dev_exchange(sh)) return ctx_dev(sh, fc);
+        *fc = ctx();
+        return GM_OK;
+    }
     // all-gather of the slots + the one-wave sum, both on the prover's stream; finish() then sees the SUMS in pinned memory
     int32_t exchange(const Shard& sh, int nacc, hipStream_t s) {
         const int32_t rc = sh.comm->all_gather_dev(sh.comm->ctx, xslot.p, xall.p, 4 * sizeof(Fr), s);
@@ -1813,6 +1821,8 @@ struct RoundScratch {
     // folds, [12] ticket word the waiting folds watch (l[0]) and their status word (l[1])
     Fr* t_slot(uint32_t round) const { return h_result + 8 + (round & 3); }
     uint32_t* ticket_word() const { return reinterpret_cast<uint32_t*>(h_result + 12); }
+    // the device copy of a pre-enqueued fold's challenge (k_fold_gate writes it)
+    Fr* fold_t() const { return reinterpret_cast<Fr*>(static_cast<char*>(counter.p) + 64); }
     static uint32_t& ticket_counter() {
         static thread_local uint32_t c = 0;
         return c;
@@ -1831,10 +1841,9 @@ struct RoundScratch {
     // tests -- wait for each other's round sums: four ranks' spinning folds of 512 workgroups each fill the device and keep the round
     // kernel of the rank everybody waits for from being scheduled.  Sharded objects therefore keep the inside gate to folds of <= 64
     // workgroups; a rank with a device of its own loses a gate launch on the larger ones.)
-    GateArgs gate_in_fold(uint32_t round, uint32_t ticket, uint64_t fold_blocks, bool sharded = false) const {
-        static const bool off = [] { const char* e = getenv("GM_FOLD_GATE_INSIDE"); return e && e[0] == '0'; }();
+    GateArgs gate_in_fold(uint32_t round, uint32_t ticket, uint64_t fold_blocks, bool sharded) const {
         GateArgs g;
-        g.bar_slot = (!off && bar && fold_blocks <= (sharded ? 64u : 512u)) ? bar + 12 * (round & 3) : nullptr;
+        g.bar_slot = (bar && fold_blocks <= (sharded ? 64u : 512u)) ? bar + 12 * (round & 3) : nullptr;
         g.ticket = ticket;
         g.status = const_cast<uint32_t*>(reinterpret_cast<volatile uint32_t*>(ticket_word())) + 1;
         g.timeout_ticks = wait_timeout_ticks();
@@ -1888,6 +1897,52 @@ struct RoundScratch {
         std::atomic_thread_fence(std::memory_order_acquire);
         for (int a = 0; a < nacc; a++) out[a] = h_result[a];
         return GM_OK;
+    }
+};
+
+// The pre-enqueued round (ScDense, ScDenseDeg2, ScVecVecDeg2): while round r is still running, its fold is enqueued behind a gate
+// that waits for the challenge t_r, and the kernel of round r + 1 behind the fold.  This holds the state of it and does the steps
+// the three objects take alike; whether to pre-enqueue, which fold runs and what follows it are the objects' own.
+struct RoundPipe {
+    uint32_t k_enq = 0;            // round kernels enqueued so far: rounds [0, k_enq)
+    uint32_t k_seq[64] = {};       // result sequence number of the enqueued round kernels
+    bool fold_pending = false;     // the fold of the current round is enqueued and waits for its challenge
+    uint32_t fold_ticket = 0;
+    // GM_SC_NO_PIPELINE=1: plain rounds (kernel, wait, fold)
+    static bool enabled() {
+        static const bool v = [] { const char* e = getenv("GM_SC_NO_PIPELINE"); return !(e && e[0] == '1'); }();
+        return v;
+    }
+    // takes a ticket and arms the gate of the fold of `round` (fold_blocks workgroups): the fold carries it inside (bar_slot of the
+    // result set), or k_fold_gate goes into the stream now and leaves the challenge at rs.fold_t() for the fold behind it
+    GateArgs arm_gate(RoundScratch& rs, uint32_t round, uint64_t fold_blocks, bool sharded, hipStream_t s) {
+        do fold_ticket = ++RoundScratch::ticket_counter(); while (fold_ticket == 0);
+        const GateArgs ga = rs.gate_in_fold(round, fold_ticket, fold_blocks, sharded);
+        if (!ga.bar_slot)
+            hipLaunchKernelGGL(k_fold_gate, dim3(1), dim3(64), 0, s, rs.t_slot(round), rs.ticket_word(), fold_ticket, rs.ticket_word() + 1,
+                               rs.fold_t(), wait_timeout_ticks());
+        return ga;
+    }
+    // the nacc sums of `round`; with a fold pending the stream cannot be synchronised (the fold waits for this thread)
+    int32_t wait_sums(RoundScratch& rs, uint32_t round, int nacc, hipStream_t s, Fr* acc) {
+        int32_t rc = rs.finish_seq(k_seq[round & 63], nacc, s, acc, !fold_pending);
+        if (rc) return rc;
+        if (rs.ticket_word()[1]) {
+            rs.ticket_word()[1] = 0;   // the staging may be shared with later objects: report once
+            return set_err(GM_ERR_STATE, "a pre-enqueued fold timed out waiting for its challenge (gm_set_wait_timeout_ms)");
+        }
+        return GM_OK;
+    }
+    // the waiting fold (and the next round kernel behind it) take it from here
+    void publish(RoundScratch& rs, uint32_t round, const Fr& t) {
+        rs.publish(round, t, fold_ticket);
+        fold_pending = false;
+    }
+    // at the object's end: never leave a waiting gate behind
+    void release(RoundScratch& rs, uint32_t round, hipStream_t s) {
+        if (!fold_pending) return;
+        rs.publish(round, fr_zero(), fold_ticket);
+        (void)hipStreamSynchronize(s);
     }
 };
 
@@ -1966,12 +2021,8 @@ static int32_t tail_stage(TailStage** out) {
 }
 
 static bool stage_enabled() {
-    // the stage kernel is itself a pre-enqueued mechanism: GM_SC_NO_PIPELINE=1 (plain rounds: kernel, sync, fold) switches it off too
-    static const bool v = [] {
-        const char* e = getenv("GM_SC_NO_TAIL");
-        const char* p = getenv("GM_SC_NO_PIPELINE");
-        return !(e && e[0] == '1') && !(p && p[0] == '1');
-    }();
+    // the stage kernel is itself a pre-enqueued mechanism: GM_SC_NO_PIPELINE=1 switches it off too
+    static const bool v = [] { const char* e = getenv("GM_SC_NO_TAIL"); return !(e && e[0] == '1') && RoundPipe::enabled(); }();
     return v;
 }
 static bool spin_for(volatile uint32_t* slot, uint32_t want) {
@@ -2110,9 +2161,8 @@ struct StageRun {
     // a: geometry, data pointers, eq pointers and pads filled by the caller
     int32_t launch(const SegPlan& sp_in, const ColPtrs& cp, const Fr* d_gamma, StageArgs a, hipStream_t s, bool may_wait = true) {
         // term split (segfn.hip.h): more, shorter evaluation chains per round when the wider grid still fits the device
-        static const bool no_split = [] { const char* e = getenv("GM_STAGE_SPLIT"); return e && e[0] == '0'; }();
         SegPlan sp_split;
-        const bool split = !no_split && seg_plan_split_terms(sp_in, &sp_split) &&
+        const bool split = seg_plan_split_terms(sp_in, &sp_split) &&
                            fits(sp_split.nseg, a.n_elems, a.n_thin > 0 ? a.n_thin : 0, a.n_dense);
         const SegPlan& sp = split ? sp_split : sp_in;
         int32_t rc = tail_stage(&st);
@@ -2626,12 +2676,22 @@ static int32_t shard_gather_columns(const Shard& sh, const Fr* const* cur, int k
     return GM_OK;
 }
 
-struct ScDensePipe {
-    static bool enabled() {
-        static const bool v = [] { const char* e = getenv("GM_SC_NO_PIPELINE"); return !(e && e[0] == '1'); }();
-        return v;
-    }
-};
+// the pre-enqueued fold of dense columns (ScDense, ScDenseDeg2): the n_out pairs of `cols` into *dst, behind the gate of `round`
+static int32_t enqueue_dense_fold(RoundPipe& pipe, RoundScratch& rs, FoldCols& cols, std::vector<Fr*>* dst, uint64_t n_out, uint32_t round,
+                                  bool sharded, hipStream_t s) {
+    cols.next(dst);
+    ColPtrs ci;
+    ColPtrsMut co;
+    for (int i = 0; i < cols.k; i++) { ci.p[i] = cols.cur[i]; co.p[i] = (*dst)[i]; }
+    const dim3 grid(ceil_div(n_out, 256), cols.k);
+    const GateArgs ga = pipe.arm_gate(rs, round, (uint64_t)grid.x * cols.k, sharded, s);
+    if (ga.bar_slot) hipLaunchKernelGGL(k_dense_fold_gated, grid, dim3(256), 0, s, ci, co, n_out, ga);
+    else hipLaunchKernelGGL(k_dense_fold_dev, grid, dim3(256), 0, s, ci, co, n_out, rs.fold_t());
+    prof_fold(96.0 * cols.k * (double)n_out);
+    GM_LAUNCH_CHECK();
+    pipe.fold_pending = true;
+    return GM_OK;
+}
 
 struct ScDense : gm_sc {
     int kind = 0;  // 0: EqWrapper(GammaWrapper(f, gamma)) with the eq column last; 1: Prod3
@@ -2667,10 +2727,7 @@ struct ScDense : gm_sc {
     }
 
     // ---- pre-enqueued small rounds, as in ScDenseDeg2
-    uint32_t k_enq = 0;
-    uint32_t k_seq[64] = {};
-    bool fold_pending = false;
-    uint32_t fold_ticket = 0;
+    RoundPipe pipe;
     std::vector<Fr*> fold_dst;
     int32_t launch_round(const Fr* const* cur_cols, uint64_t npairs, uint32_t round) {
         ColPtrs cp;
@@ -2679,12 +2736,8 @@ struct ScDense : gm_sc {
         const int ny = split ? D * (kind == 1 ? 1 : sp.nseg) : 1;
         const dim3 grid = round_grid(npairs, ny);
         FinishCtx fc;
-        if (RoundScratch::dev_exchange(sh)) {
-            int32_t rc = rs.ctx_dev(sh, &fc);
-            if (rc) return rc;
-        } else {
-            fc = rs.ctx();
-        }
+        int32_t rc = rs.round_ctx(sh, &fc);
+        if (rc) return rc;
         const int lean = (kind == 0 && D == 3 && !split && cols.k <= 7) ? lean_prim_of(sp) : 0;
         if (kind == 2) {
             FoldedCols fcols;
@@ -2723,16 +2776,11 @@ struct ScDense : gm_sc {
         else
             return set_err(GM_ERR_INVALID, "unsupported degree %d", D);
         GM_LAUNCH_CHECK();
-        k_seq[round & 63] = fc.seq;
+        pipe.k_seq[round & 63] = fc.seq;
         if (split || !(lean || (kind == 1 && D == 3))) prof_small_round(64.0 * cols.k * (double)npairs);
         return GM_OK;
     }
-    ~ScDense() override {
-        if (fold_pending) {  // never leave a waiting gate behind
-            rs.publish(round_idx, fr_zero(), fold_ticket);
-            (void)hipStreamSynchronize(stream);
-        }
-    }
+    ~ScDense() override { pipe.release(rs, round_idx, stream); }
 
     int32_t unipoly(std::vector<Fr>* coeffs) override {
         if (round_idx >= num_vars) return set_err(GM_ERR_STATE, "the protocol has already ended (sumcheck.rs:279)");
@@ -2743,36 +2791,19 @@ struct ScDense : gm_sc {
             }
             const uint64_t npairs = 1ull << (loc_vars - 1);
             const bool split = npairs <= SC_SPLIT_MAX_PAIRS;
-            const bool piped = split && !sh.comm && ScDensePipe::enabled() && (rs.own_pinned || pinned_exclusive() || k_enq > round_idx);
-            if (k_enq <= round_idx) {
+            const bool piped = split && !sh.comm && RoundPipe::enabled() && (rs.pinned_ours() || pipe.k_enq > round_idx);
+            if (pipe.k_enq <= round_idx) {
                 int32_t rc = launch_round(cols.cur.data(), npairs, round_idx);
                 if (rc) return rc;
-                k_enq = round_idx + 1;
+                pipe.k_enq = round_idx + 1;
             }
-            if (piped && !fold_pending && round_idx + 1 < num_vars && k_enq == round_idx + 1) {
-                // small rounds: enqueue this round's fold behind a gate (k_fold_gate) and the next round's kernel now
-                cols.next(&fold_dst);
-                ColPtrs ci;
-                ColPtrsMut co;
-                std::vector<const Fr*> cn(cols.k);
-                for (int i = 0; i < cols.k; i++) { ci.p[i] = cols.cur[i]; co.p[i] = fold_dst[i]; cn[i] = fold_dst[i]; }
-                fold_ticket = ++RoundScratch::ticket_counter();
-                if (fold_ticket == 0) fold_ticket = ++RoundScratch::ticket_counter();
-                Fr* d_t = reinterpret_cast<Fr*>(static_cast<char*>(rs.counter.p) + 64);
-                const GateArgs ga = rs.gate_in_fold(round_idx, fold_ticket, (uint64_t)ceil_div(npairs, 256) * cols.k);
-                if (ga.bar_slot) {
-                    hipLaunchKernelGGL(k_dense_fold_gated, dim3(ceil_div(npairs, 256), cols.k), dim3(256), 0, stream, ci, co, npairs, ga);
-                } else {
-                    hipLaunchKernelGGL(k_fold_gate, dim3(1), dim3(64), 0, stream, rs.t_slot(round_idx), rs.ticket_word(), fold_ticket,
-                                       rs.ticket_word() + 1, d_t, wait_timeout_ticks());
-                    hipLaunchKernelGGL(k_dense_fold_dev, dim3(ceil_div(npairs, 256), cols.k), dim3(256), 0, stream, ci, co, npairs, d_t);
-                }
-                prof_fold(96.0 * cols.k * (double)npairs);
-                GM_LAUNCH_CHECK();
-                fold_pending = true;
-                int32_t rc = launch_round(cn.data(), npairs >> 1, round_idx + 1);
+            if (piped && !pipe.fold_pending && round_idx + 1 < num_vars && pipe.k_enq == round_idx + 1) {
+                // small rounds: enqueue this round's fold behind a gate and the next round's kernel now
+                int32_t rc = enqueue_dense_fold(pipe, rs, cols, &fold_dst, npairs, round_idx, false, stream);
                 if (rc) return rc;
-                k_enq = round_idx + 2;
+                rc = launch_round(fold_dst.data(), npairs >> 1, round_idx + 1);
+                if (rc) return rc;
+                pipe.k_enq = round_idx + 2;
             }
             Fr acc[4];
             const bool devx = RoundScratch::dev_exchange(sh);
@@ -2780,12 +2811,8 @@ struct ScDense : gm_sc {
                 int32_t rc = rs.exchange(sh, D, stream);
                 if (rc) return rc;
             }
-            int32_t rc = rs.finish_seq(k_seq[round_idx & 63], D, stream, acc, !fold_pending);
+            int32_t rc = pipe.wait_sums(rs, round_idx, D, stream, acc);
             if (rc) return rc;
-            if (rs.ticket_word()[1]) {
-                rs.ticket_word()[1] = 0;   // the staging may be shared with later objects: report once
-                return set_err(GM_ERR_STATE, "a pre-enqueued fold timed out waiting for its challenge (gm_set_wait_timeout_ms)");
-            }
             if (sh.comm && !devx) {
                 rc = shard_sum_fr(sh, acc, D);
                 if (rc) return rc;
@@ -2803,9 +2830,8 @@ struct ScDense : gm_sc {
     int32_t bind(const Fr& t) override {
         if (round_idx >= num_vars) return set_err(GM_ERR_STATE, "the protocol has already ended (sumcheck.rs:264)");
         if (!has_cached) return set_err(GM_ERR_STATE, "should evaluate unipoly before binding (sumcheck.rs:271)");
-        if (fold_pending) {
-            rs.publish(round_idx, t, fold_ticket);
-            fold_pending = false;
+        if (pipe.fold_pending) {
+            pipe.publish(rs, round_idx, t);
             cols.commit(fold_dst);
         } else {
             std::vector<Fr*> dst;
@@ -2882,7 +2908,7 @@ struct ScDenseDeg2 : gm_sc {
         // rounds inside a running tail launch (its first round goes through unipoly_pipelined, which handles a launch that left at the
         // residency barrier; a launch adopted from a VecVec object has been running for rounds)
         if (tail_active && round_idx >= tail_r0 && (round_idx > tail_r0 || stage_adopted)) return unipoly_tail(coeffs);
-        if (sh.comm && loc_vars <= shard_gather_log() && !fold_pending) {
+        if (sh.comm && loc_vars <= shard_gather_log() && !pipe.fold_pending) {
             int32_t rc = gather_cols();
             if (rc) return rc;
         }
@@ -2893,16 +2919,12 @@ struct ScDenseDeg2 : gm_sc {
         const bool devx = RoundScratch::dev_exchange(sh);
         // sharded with the round sums meeting on the host: the device side of a round is the unsharded one
         // results of pre-enqueued kernels land in the pinned staging: it must be this object's alone for the duration
-        if (!devx && pipeline_enabled() && (rs.own_pinned || pinned_exclusive() || k_enq > round_idx))
+        if (!devx && RoundPipe::enabled() && (rs.pinned_ours() || pipe.k_enq > round_idx))
             return unipoly_pipelined(coeffs, npairs, eq_cur, cp);
         FinishCtx fc0;
-        if (devx) {
-            int32_t rc = rs.ctx_dev(sh, &fc0);
-            if (rc) return rc;
-        } else {
-            fc0 = rs.ctx();
-        }
-        int32_t rc = launch_round_deg2(stream, sp, cols.cur.data(), cols.k, eq_cur, d_gamma.fr(), npairs, nullptr, fc0);
+        int32_t rc = rs.round_ctx(sh, &fc0);
+        if (rc) return rc;
+        rc = launch_round_deg2(stream, sp, cols.cur.data(), cols.k, eq_cur, d_gamma.fr(), npairs, nullptr, fc0);
         if (rc) return rc;
         if (devx) {
             int32_t rc = rs.exchange(sh, 2, stream);
@@ -2915,8 +2937,12 @@ struct ScDenseDeg2 : gm_sc {
             rc = shard_sum_fr(sh, acc, 2);
             if (rc) return rc;
         }
-        // full-length dense columns: sum of eq = 1, the trailing pad term (dense_eq.rs:141-146) vanishes
-        const Fr total1 = fr_mul(acc[0], multiplier), total2 = fr_mul(acc[1], multiplier);
+        return round_poly(acc[0], acc[1], coeffs);
+    }
+    // the round polynomial from the round's two sums over the columns (full-length dense columns: sum of eq = 1, the trailing pad
+    // term of dense_eq.rs:141-146 vanishes)
+    int32_t round_poly(const Fr& s1, const Fr& s2, std::vector<Fr>* coeffs) {
+        const Fr total1 = fr_mul(s1, multiplier), total2 = fr_mul(s2, multiplier);
         if (inv_eq0.empty()) inv_eq0 = batch_inv_one_minus(point);  // first round: point is still complete
         cached = from12_inv(total1, total2, point.back(), inv_eq0[point.size() - 1], claim_);
         has_cached = true;
@@ -2925,15 +2951,8 @@ struct ScDenseDeg2 : gm_sc {
     }
 
     // ---- pre-enqueued small rounds (see k_fold_gate)
-    uint32_t k_enq = 0;            // round kernels enqueued so far: rounds [0, k_enq)
-    uint32_t k_seq[64] = {};       // result sequence number of the enqueued round kernels
-    bool fold_pending = false;     // the fold of round `round_idx` is enqueued and waits for its challenge
-    uint32_t fold_ticket = 0;
+    RoundPipe pipe;
     std::vector<Fr*> fold_dst;
-    static bool pipeline_enabled() {
-        static const bool v = [] { const char* e = getenv("GM_SC_NO_PIPELINE"); return !(e && e[0] == '1'); }();
-        return v;
-    }
     // the round kernel of a pre-enqueued round, by size: split mode for small rounds, the lean kernel of a single-primitive layer or
     // the generic kernel for large ones (large rounds are pre-enqueued too: the fold and the next round kernel are then already
     // in the stream when the challenge arrives, ~10 us of launch latency per round)
@@ -2941,7 +2960,7 @@ struct ScDenseDeg2 : gm_sc {
         const FinishCtx fc = rs.ctx();
         int32_t rc = launch_round_deg2(stream, sp, cp.p, cols.k, eq, d_gamma.fr(), npairs, nullptr, fc);
         if (rc) return rc;
-        k_seq[round & 63] = fc.seq;
+        pipe.k_seq[round & 63] = fc.seq;
         return GM_OK;
     }
     // ---- persistent stage (see k_stage): rounds [tail_r0, num_vars) run inside one launch
@@ -2983,7 +3002,7 @@ struct ScDenseDeg2 : gm_sc {
         tail_active = true;
         tail_r0 = 0;
         host_r0 = (uint32_t)run->n_dense;
-        k_enq = num_vars;
+        pipe.k_enq = num_vars;
     }
     // ---- the last rounds on the host (see stage_host_rounds): rounds [host_r0, num_vars) over the elements the launch left
     uint32_t host_r0 = 0xffffffffu;
@@ -3070,23 +3089,18 @@ struct ScDenseDeg2 : gm_sc {
         Fr a1, a2;
         int32_t rc = tail_round_sums(&a1, &a2);
         if (rc) return rc;
-        const Fr total1 = fr_mul(a1, multiplier), total2 = fr_mul(a2, multiplier);
-        if (inv_eq0.empty()) inv_eq0 = batch_inv_one_minus(point);
-        cached = from12_inv(total1, total2, point.back(), inv_eq0[point.size() - 1], claim_);
-        has_cached = true;
-        *coeffs = cached;
-        return GM_OK;
+        return round_poly(a1, a2, coeffs);
     }
     int32_t unipoly_pipelined(std::vector<Fr>* coeffs, uint64_t npairs, const Fr* eq_cur, const ColPtrs& cp) {
         const uint32_t r = round_idx;
         // (a sharded object keeps to pre-enqueued rounds: whether a tail launch runs would have to be agreed between the ranks, as the
         // VecVec object does for its stage; sharded dense objects of the image part are the dense stages of VecVec layers, which
         // are inside that launch already)
-        const bool tail_ok = !tail_denied && !sh.comm && stage_enabled() && sp.nseg <= 32 && (rs.own_pinned || pinned_exclusive());
-        if (!tail_active && tail_ok && stage_fits(r, npairs) && k_enq <= r) {
+        const bool tail_ok = !tail_denied && !sh.comm && stage_enabled() && sp.nseg <= 32 && rs.pinned_ours();
+        if (!tail_active && tail_ok && stage_fits(r, npairs) && pipe.k_enq <= r) {
             int32_t rc = launch_tail(cp, r, npairs);   // the object starts small: everything runs in the tail
             if (rc) return rc;
-            k_enq = num_vars;
+            pipe.k_enq = num_vars;
         }
         if (tail_active && r >= tail_r0) {
             Fr a1, a2;
@@ -3097,125 +3111,80 @@ struct ScDenseDeg2 : gm_sc {
                 tail_active = false;
                 tail_denied = true;
                 host_r0 = 0xffffffffu;
-                k_enq = r;
+                pipe.k_enq = r;
                 return unipoly_pipelined(coeffs, npairs, eq_cur, cp);
             }
             if (rc) return rc;
-            const Fr total1 = fr_mul(a1, multiplier), total2 = fr_mul(a2, multiplier);
-            if (inv_eq0.empty()) inv_eq0 = batch_inv_one_minus(point);
-            cached = from12_inv(total1, total2, point.back(), inv_eq0[point.size() - 1], claim_);
-            has_cached = true;
-            *coeffs = cached;
-            return GM_OK;
+            return round_poly(a1, a2, coeffs);
         }
-        if (k_enq <= r) {  // the first small round of this object: nothing was enqueued ahead
+        if (pipe.k_enq <= r) {  // the first small round of this object: nothing was enqueued ahead
             int32_t rc = launch_small_round(cp, eq_cur, npairs, r);
             if (rc) return rc;
-            k_enq = r + 1;
+            pipe.k_enq = r + 1;
         }
         // (sharded: the round at which the ranks gather their slices is not enqueued ahead -- its kernel runs on the gathered columns)
-        if (!fold_pending && (sh.comm ? loc_vars > shard_gather_log() + 1 : loc_vars >= 2) && k_enq == r + 1) {
+        if (!pipe.fold_pending && (sh.comm ? loc_vars > shard_gather_log() + 1 : loc_vars >= 2) && pipe.k_enq == r + 1) {
             // enqueue fold r (waiting for t_r) and round kernel r + 1 while round r is still running
-            cols.next(&fold_dst);
-            ColPtrs ci;
-            ColPtrsMut co;
+            int32_t rc = enqueue_dense_fold(pipe, rs, cols, &fold_dst, npairs, r, sh.comm != nullptr, stream);
+            if (rc) return rc;
             ColPtrs cn;
-            for (int i = 0; i < cols.k; i++) { ci.p[i] = cols.cur[i]; co.p[i] = fold_dst[i]; cn.p[i] = fold_dst[i]; }
-            fold_ticket = ++RoundScratch::ticket_counter();
-            if (fold_ticket == 0) fold_ticket = ++RoundScratch::ticket_counter();
-            const uint64_t n_out = npairs;
-            Fr* d_t = reinterpret_cast<Fr*>(static_cast<char*>(rs.counter.p) + 64);
-            const GateArgs ga = rs.gate_in_fold(r, fold_ticket, (uint64_t)ceil_div(n_out, 256) * cols.k, sh.comm != nullptr);
-            if (ga.bar_slot) {
-                hipLaunchKernelGGL(k_dense_fold_gated, dim3(ceil_div(n_out, 256), cols.k), dim3(256), 0, stream, ci, co, n_out, ga);
-            } else {
-                hipLaunchKernelGGL(k_fold_gate, dim3(1), dim3(64), 0, stream, rs.t_slot(r), rs.ticket_word(), fold_ticket, rs.ticket_word() + 1, d_t,
-                                   wait_timeout_ticks());
-                hipLaunchKernelGGL(k_dense_fold_dev, dim3(ceil_div(n_out, 256), cols.k), dim3(256), 0, stream, ci, co, n_out, d_t);
-            }
-            prof_fold(96.0 * cols.k * (double)n_out);
-            GM_LAUNCH_CHECK();
-            fold_pending = true;
+            for (int i = 0; i < cols.k; i++) cn.p[i] = fold_dst[i];
             bool staged = false;
             if (tail_ok && stage_fits(r + 1, npairs >> 1)) {   // everything after this fold runs in one launch
                 // this round's gate is in the stream, waiting for this thread: try only (StageSlots)
-                int32_t rc = launch_tail(cn, r + 1, npairs >> 1, false);
+                rc = launch_tail(cn, r + 1, npairs >> 1, false);
                 if (rc && rc != GM_STAGE_BUSY) return rc;
                 staged = rc == GM_OK;
             }
             if (staged) {
-                k_enq = num_vars;
+                pipe.k_enq = num_vars;
             } else {
                 const Fr* eq_next = eq_at(num_vars - 2 - r, glob_off >> 2);
-                int32_t rc = launch_small_round(cn, eq_next, npairs >> 1, r + 1);
+                rc = launch_small_round(cn, eq_next, npairs >> 1, r + 1);
                 if (rc) return rc;
-                k_enq = r + 2;
+                pipe.k_enq = r + 2;
             }
         }
         Fr acc[4];
-        int32_t rc = rs.finish_seq(k_seq[r & 63], 2, stream, acc, !fold_pending);
+        int32_t rc = pipe.wait_sums(rs, r, 2, stream, acc);
         if (rc) return rc;
-        if (rs.ticket_word()[1]) {
-                rs.ticket_word()[1] = 0;   // the staging may be shared with later objects: report once
-                return set_err(GM_ERR_STATE, "a pre-enqueued fold timed out waiting for its challenge (gm_set_wait_timeout_ms)");
-            }
         if (sh.comm) {
             rc = shard_sum_fr(sh, acc, 2);
             if (rc) return rc;
         }
-        const Fr total1 = fr_mul(acc[0], multiplier), total2 = fr_mul(acc[1], multiplier);
-        if (inv_eq0.empty()) inv_eq0 = batch_inv_one_minus(point);
-        cached = from12_inv(total1, total2, point.back(), inv_eq0[point.size() - 1], claim_);
-        has_cached = true;
-        *coeffs = cached;
-        return GM_OK;
+        return round_poly(acc[0], acc[1], coeffs);
     }
-    ~ScDenseDeg2() override {
-        if (fold_pending) {   // never leave a waiting kernel behind (a gate here; the stage launch releases its own waiters)
-            rs.publish(round_idx, fr_zero(), fold_ticket);
-            (void)hipStreamSynchronize(stream);
-        }
-    }
+    // (a pending gate; the stage launch releases its own waiters)
+    ~ScDenseDeg2() override { pipe.release(rs, round_idx, stream); }
 
     int32_t bind(const Fr& t) override {
         if (!has_cached) return set_err(GM_ERR_STATE, "bind before unipoly (dense_eq.rs:105 unwrap)");
         multiplier = fr_mul(multiplier, eq_bind_factor(point.back(), t));
         if (tail_active && round_idx >= tail_r0) {   // the fold happens inside the tail kernel
             tail_publish(t);
-            point.pop_back();
-            round_idx++;
-            loc_vars--;
-            glob_off >>= 1;
-            claim_ = evaluate_univar(cached, t);
-            has_cached = false;
-            return GM_OK;
-        }
-        if (fold_pending) {
-            rs.publish(round_idx, t, fold_ticket);   // the waiting fold and the next round kernel take it from here
-            fold_pending = false;
+        } else if (pipe.fold_pending) {
+            pipe.publish(rs, round_idx, t);
             cols.commit(fold_dst);
-            point.pop_back();
-            round_idx++;
-            loc_vars--;
-            glob_off >>= 1;
-            claim_ = evaluate_univar(cached, t);
-            has_cached = false;
-            return GM_OK;
+        } else {
+            std::vector<Fr*> dst;
+            cols.next(&dst);
+            const uint64_t n_out = 1ull << (loc_vars - 1);
+            int32_t rc = launch_dense_fold(cols.cur.data(), dst.data(), cols.k, n_out, t, stream);
+            if (rc) return rc;
+            prof_fold(96.0 * cols.k * (double)n_out);
+            cols.commit(dst);
         }
-        std::vector<Fr*> dst;
-        cols.next(&dst);
-        const uint64_t n_out = 1ull << (loc_vars - 1);
-        int32_t rc = launch_dense_fold(cols.cur.data(), dst.data(), cols.k, n_out, t, stream);
-        if (rc) return rc;
-        prof_fold(96.0 * cols.k * (double)n_out);
-        cols.commit(dst);
+        advance(t);
+        return GM_OK;
+    }
+    // the round is bound to t: its variable leaves the point
+    void advance(const Fr& t) {
         point.pop_back();
         round_idx++;
         loc_vars--;
         glob_off >>= 1;
         claim_ = evaluate_univar(cached, t);
         has_cached = false;
-        return GM_OK;
     }
 
     int32_t final_evals(std::vector<Fr>* out) override {
@@ -3291,7 +3260,7 @@ struct ScVecVecDeg2 : gm_sc {
         // polynomial decides it -- by exchanging one word: a rank whose launch could not be made or did not become resident says so
         // and everybody runs the layer's remaining rounds as ordinary kernels.
         const bool deciding = shard_host && !stage_decided && cur_max_len == 2 && stage_shape_ok();
-        if (!stage_active && k_enq <= already_bound && cur_max_len == 2 && stage_ok() && (!shard_host || deciding)) {
+        if (!stage_active && pipe.k_enq <= already_bound && cur_max_len == 2 && stage_ok() && (!shard_host || deciding)) {
             // every row is down to one pair: this round, the rest of the sparse stage and the whole dense stage run in one launch.
             // A sharded launch only TRIES for its share of the device's co-residency budget: ranks that are threads of one process
             // share that budget, and the rank holding it waits for this one's round sums -- waiting here would close the cycle.
@@ -3307,7 +3276,7 @@ struct ScVecVecDeg2 : gm_sc {
                 stage.reset();
                 stage_active = false;
                 stage_denied = true;
-                k_enq = already_bound;
+                pipe.k_enq = already_bound;
             } else if (rc) return rc;
             else healthy = true;
         }
@@ -3328,7 +3297,7 @@ struct ScVecVecDeg2 : gm_sc {
                     g_stage_left++;
                     stage.reset();
                     stage_active = false;
-                    k_enq = already_bound;
+                    pipe.k_enq = already_bound;
                 }
                 stage_denied = true;
             }
@@ -3338,75 +3307,8 @@ struct ScVecVecDeg2 : gm_sc {
             if (rc) return rc;
         }
         if (!stage_active) {
-        // every sparse round (large ones too: the fold and the next round kernel are then already in the stream when the
-        // challenge arrives, ~8 us of launch latency per round) enqueues its fold behind a gate and the next round's kernel
-        const bool piped = !devx && ScDenseDeg2::pipeline_enabled() &&
-                           (rs.own_pinned || pinned_exclusive() || k_enq > already_bound);
-        if (k_enq <= already_bound) {
-            int32_t rc = launch_sparse_round(cur.data(), off_cur, cells_bound, already_bound);
+            int32_t rc = sparse_round_sums(devx, acc);
             if (rc) return rc;
-            k_enq = already_bound + 1;
-        }
-        if (piped && !fold_pending && k_enq == already_bound + 1 && (uint32_t)binding_var_idx > col_logsize &&
-            already_bound + 1 < n_off_tables && k <= 16) {
-            // enqueue the fold of this round (behind a gate that waits for t) and the next round's kernel now
-            nx_to_a = !started || !cur_is_a;
-            nx_off = off_tab + (uint64_t)(already_bound + 1) * (nrows + 1);
-            nx_bound = cells_bound / 2 + nrows;
-            ColPtrs ci;
-            ColPtrsMut co;
-            PadCols pd;
-            nx_cur.resize(k);
-            for (int i = 0; i < k; i++) {
-                ci.p[i] = cur[i];
-                co.p[i] = nx_to_a ? bufA[i]->fr() : bufB[i]->fr();
-                pd.v[i] = row_pad[i];
-                nx_cur[i] = co.p[i];
-            }
-            fold_ticket = ++RoundScratch::ticket_counter();
-            if (fold_ticket == 0) fold_ticket = ++RoundScratch::ticket_counter();
-            Fr* d_t = reinterpret_cast<Fr*>(static_cast<char*>(rs.counter.p) + 64);
-            const GateArgs ga = rs.gate_in_fold(already_bound, fold_ticket, (uint64_t)ceil_div(nx_bound, SC_THREADS) * ((k + 1) / 2), sh.comm != nullptr);
-            if (!ga.bar_slot)
-                hipLaunchKernelGGL(k_fold_gate, dim3(1), dim3(64), 0, stream, rs.t_slot(already_bound), rs.ticket_word(), fold_ticket,
-                                   rs.ticket_word() + 1, d_t, wait_timeout_ticks());
-            hipLaunchKernelGGL(k_vv_fold, dim3(ceil_div(nx_bound, SC_THREADS), (k + 1) / 2), dim3(SC_THREADS), 0, stream, ci, co, off_cur,
-                               nx_off, nrows, fr_zero(), pd, (const Fr*)d_t, k, coarse_for(nx_off), ga);
-            GM_LAUNCH_CHECK();
-            prof_fold(96.0 * k * (double)(cells_bound / 2));
-            fold_pending = true;
-            const uint32_t half = cur_max_len / 2, next_max = half + (half & 1);
-            bool staged = false;
-            if (next_max == 2 && stage_ok()) {   // the fold leaves one pair per row: everything after it runs in one launch
-                // this round's gate is in the stream, waiting for this thread: try only (StageSlots)
-                int32_t rc = launch_stage(nx_cur.data(), nx_off, already_bound + 1, false);
-                if (rc && rc != GM_STAGE_BUSY) return rc;
-                staged = rc == GM_OK;
-            }
-            if (staged) {
-                stage_active = false;   // this round still reports through its own kernel; bind() switches over
-                stage_armed = true;
-                k_enq = 0x7fffffffu;
-            } else {
-                int32_t rc = launch_sparse_round(nx_cur.data(), nx_off, nx_bound, already_bound + 1);
-                if (rc) return rc;
-                k_enq = already_bound + 2;
-            }
-        }
-        if (devx) {
-            int32_t rc = rs.exchange(sh, 3, stream);
-            if (rc) return rc;
-        }
-        int32_t rc = rs.finish_seq(k_seq[already_bound & 63], 3, stream, acc, !fold_pending);
-        if (rc) return rc;
-        if (rs.ticket_word()[1]) {
-                rs.ticket_word()[1] = 0;   // the staging may be shared with later objects: report once
-                return set_err(GM_ERR_STATE, "a pre-enqueued fold timed out waiting for its challenge (gm_set_wait_timeout_ms)");
-            }
-        if (sh.comm && !devx) {
-            rc = shard_sum_fr(sh, acc, 3);
-            if (rc) return rc;
-        }
         }
         const Fr* w = acc + 2;
         // pads: f(row_pad..) weighted by W, f(col_pad..) by the coefficient tail (vecvec_eq.rs:309-315, 345-371)
@@ -3428,6 +3330,57 @@ struct ScVecVecDeg2 : gm_sc {
         cached = from12_inv(total1, total2, point[binding_var_idx], inv_eq0[binding_var_idx], claim_);
         has_cached = true;
         *coeffs = cached;
+        return GM_OK;
+    }
+    // the sums of a round outside the stage kernel.  Every sparse round (large ones too: the fold and the next round kernel are then
+    // already in the stream when the challenge arrives, ~8 us of launch latency per round) enqueues its fold behind a gate and the
+    // next round's kernel.
+    int32_t sparse_round_sums(bool devx, Fr* acc) {
+        const bool piped = !devx && RoundPipe::enabled() && (rs.pinned_ours() || pipe.k_enq > already_bound);
+        if (pipe.k_enq <= already_bound) {
+            int32_t rc = launch_sparse_round(cur.data(), off_cur, cells_bound, already_bound);
+            if (rc) return rc;
+            pipe.k_enq = already_bound + 1;
+        }
+        if (piped && !pipe.fold_pending && pipe.k_enq == already_bound + 1 && (uint32_t)binding_var_idx > col_logsize &&
+            already_bound + 1 < n_off_tables && k <= 16) {
+            // enqueue the fold of this round (behind a gate that waits for t) and the next round's kernel now
+            ColPtrs ci;
+            ColPtrsMut co;
+            PadCols pd;
+            next_fold(&ci, &co, &pd);
+            const dim3 grid(ceil_div(nx_bound, SC_THREADS), (k + 1) / 2);
+            const GateArgs ga = pipe.arm_gate(rs, already_bound, (uint64_t)grid.x * grid.y, sh.comm != nullptr, stream);
+            hipLaunchKernelGGL(k_vv_fold, grid, dim3(SC_THREADS), 0, stream, ci, co, off_cur, nx_off, nrows, fr_zero(), pd,
+                               (const Fr*)rs.fold_t(), k, coarse_for(nx_off), ga);
+            GM_LAUNCH_CHECK();
+            prof_fold(96.0 * k * (double)(cells_bound / 2));
+            pipe.fold_pending = true;
+            const uint32_t half = cur_max_len / 2, next_max = half + (half & 1);
+            bool staged = false;
+            if (next_max == 2 && stage_ok()) {   // the fold leaves one pair per row: everything after it runs in one launch
+                // this round's gate is in the stream, waiting for this thread: try only (StageSlots)
+                int32_t rc = launch_stage(nx_cur.data(), nx_off, already_bound + 1, false);
+                if (rc && rc != GM_STAGE_BUSY) return rc;
+                staged = rc == GM_OK;
+            }
+            if (staged) {
+                stage_active = false;   // this round still reports through its own kernel; bind() switches over
+                stage_armed = true;
+                pipe.k_enq = 0x7fffffffu;
+            } else {
+                int32_t rc = launch_sparse_round(nx_cur.data(), nx_off, nx_bound, already_bound + 1);
+                if (rc) return rc;
+                pipe.k_enq = already_bound + 2;
+            }
+        }
+        if (devx) {
+            int32_t rc = rs.exchange(sh, 3, stream);
+            if (rc) return rc;
+        }
+        int32_t rc = pipe.wait_sums(rs, already_bound, 3, stream, acc);
+        if (rc) return rc;
+        if (sh.comm && !devx) return shard_sum_fr(sh, acc, 3);
         return GM_OK;
     }
 
@@ -3502,18 +3455,28 @@ struct ScVecVecDeg2 : gm_sc {
         }
         stage_active = true;
         stage_r0 = ab0;
-        k_enq = 0x7fffffffu;
+        pipe.k_enq = 0x7fffffffu;
         return GM_OK;
     }
 
     // ---- pre-enqueued small sparse rounds (same scheme as ScDenseDeg2's, see k_fold_gate); rounds are indexed by already_bound
-    uint32_t k_enq = 0;
-    uint32_t k_seq[64] = {};
-    bool fold_pending = false, nx_to_a = false;
-    uint32_t fold_ticket = 0;
+    RoundPipe pipe;
+    bool nx_to_a = false;          // the destination of the current round's fold (next_fold): the next round's columns and layout
     const uint32_t* nx_off = nullptr;
     uint64_t nx_bound = 0;
     std::vector<const Fr*> nx_cur;
+    void next_fold(ColPtrs* ci, ColPtrsMut* co, PadCols* pd) {
+        nx_to_a = !started || !cur_is_a;
+        nx_off = off_tab + (uint64_t)(already_bound + 1) * (nrows + 1);
+        nx_bound = cells_bound / 2 + nrows;
+        nx_cur.resize(k);
+        for (int i = 0; i < k; i++) {
+            ci->p[i] = cur[i];
+            co->p[i] = nx_to_a ? bufA[i]->fr() : bufB[i]->fr();
+            pd->v[i] = row_pad[i];
+            nx_cur[i] = co->p[i];
+        }
+    }
     int32_t launch_sparse_round(const Fr* const* cols_now, const uint32_t* off, uint64_t cb, uint32_t ab) {
         // eq level: row_eq_poly_seq[len - 1 - already_bound]  (vecvec.rs:129-135) and its prefix sums
         const size_t lvl = eq_level_len.size() - 1 - ab;
@@ -3521,115 +3484,71 @@ struct ScVecVecDeg2 : gm_sc {
         const Fr* eq_pre = d_prefix.fr() + eq_level_off[lvl] + lvl;  // level l has len+1 prefix entries
         const VVArgs va{off, nrows, d_row_coef.fr() + row_base, eq_pre, coarse_for(off)};
         FinishCtx fc;
-        if (RoundScratch::dev_exchange(sh)) {
-            int32_t rc = rs.ctx_dev(sh, &fc);
-            if (rc) return rc;
-        } else {
-            fc = rs.ctx();
-        }
-        int32_t rc = launch_round_deg2(stream, sp, cols_now, k, eq_row, d_gamma.fr(), cb / 2, &va, fc);
+        int32_t rc = rs.round_ctx(sh, &fc);
         if (rc) return rc;
-        k_seq[ab & 63] = fc.seq;
+        rc = launch_round_deg2(stream, sp, cols_now, k, eq_row, d_gamma.fr(), cb / 2, &va, fc);
+        if (rc) return rc;
+        pipe.k_seq[ab & 63] = fc.seq;
         return GM_OK;
     }
-    ~ScVecVecDeg2() override {
-        if (fold_pending) {  // never leave a waiting gate behind
-            rs.publish(already_bound, fr_zero(), fold_ticket);
-            (void)hipStreamSynchronize(stream);
-        }
-    }
+    ~ScVecVecDeg2() override { pipe.release(rs, already_bound, stream); }
     uint32_t n_off_tables = 0;
 
     int32_t bind(const Fr& t) override {
         if (dense2) return dense2->bind(t);
         if (dense) return dense->bind(t);
         if (!has_cached) return set_err(GM_ERR_STATE, "bind before unipoly (vecvec_eq.rs:299 unwrap)");
+        const bool sparse = (uint32_t)binding_var_idx > col_logsize;   // sparse bind (vecvec_eq.rs:295-300)
         if (stage_active) {   // the fold happens inside the stage kernel
             stage->publish((int)(already_bound - stage_r0), t);
-            const Fr mult_next = fr_mul(multiplier, eq_bind_factor(point[binding_var_idx], t));
-            const Fr claim_next = evaluate_univar(cached, t);
-            has_cached = false;
-            if ((uint32_t)binding_var_idx > col_logsize) {   // sparse bind (vecvec_eq.rs:295-300)
-                multiplier = mult_next;
-                claim_ = claim_next;
-                row_logsize--;
-                binding_var_idx--;
-                already_bound++;
+            if (sparse) {
+                sparse_advance(t);
                 return GM_OK;
             }
             // bind_into_dense (vecvec_eq.rs:157-190): the launch goes on with the dense stage; the host side is the eq-factored object
-            std::unique_ptr<ScDenseDeg2> d(new ScDenseDeg2());
-            d->stream = stream;
-            d->sp = sp;
-            d->num_vars = col_logsize;
-            d->sh = sh;                              // sharded: the launch holds this rank's slice; host_collect gathers what it leaves
-            d->loc_vars = col_logsize - sh.lg;
-            d->glob_off = row_base;
-            d->gamma_pows = gamma_pows;
-            d->point.assign(point.begin(), point.begin() + col_logsize);
-            d->multiplier = mult_next;
-            d->claim_ = claim_next;
+            std::unique_ptr<ScDenseDeg2> d = dense_deg2_handover(t);
             d->cols.k = k;
             d->cols.cur.assign(k, nullptr);
-            // 1 / (1 - point_j) of the vertical coordinates: already inverted with the row coordinates (a field inversion costs the
-            // host ~15 us, and this is the moment every block of the launch is waiting for the next challenge)
-            if (inv_eq0.size() >= col_logsize) d->inv_eq0.assign(inv_eq0.begin(), inv_eq0.begin() + col_logsize);
             d->adopt_stage(stage);
+            has_cached = false;
             dense2 = std::move(d);
             return GM_OK;
         }
-        if ((uint32_t)binding_var_idx > col_logsize) {
-            // sparse bind (vecvec_eq.rs:295-300)
-            if (fold_pending) {  // the fold is already in the stream: hand it the challenge
-                rs.publish(already_bound, t, fold_ticket);
-                fold_pending = false;
-                for (int i = 0; i < k; i++) cur[i] = nx_cur[i];
-                off_cur = nx_off;
-                cur_is_a = nx_to_a;
-                started = true;
-                cells_bound = nx_bound;
-                { const uint32_t half = cur_max_len / 2; cur_max_len = half + (half & 1); }
-                if (stage_armed) { stage_armed = false; stage_active = true; }   // the stage kernel is behind this fold in the stream
-                row_logsize--;
-                multiplier = fr_mul(multiplier, eq_bind_factor(point[binding_var_idx], t));
-                binding_var_idx--;
-                already_bound++;
-                claim_ = evaluate_univar(cached, t);
-                has_cached = false;
-                return GM_OK;
-            }
-            const bool to_a = !started || !cur_is_a;
+        if (!sparse) return bind_into_dense(t);
+        if (pipe.fold_pending) {   // the fold is already in the stream: hand it the challenge
+            pipe.publish(rs, already_bound, t);
+            if (stage_armed) { stage_armed = false; stage_active = true; }   // the stage kernel is behind this fold in the stream
+        } else {
             if (already_bound + 1 >= n_off_tables) return set_err(GM_ERR_STATE, "more sparse binds than row variables");
-            const uint32_t* off_next = off_tab + (uint64_t)(already_bound + 1) * (nrows + 1);
-            const uint64_t new_bound = cells_bound / 2 + nrows;
+            if (k > 16) return set_err(GM_ERR_INVALID, "VecVec sumcheck supports at most 16 polynomials");
             ColPtrs ci;
             ColPtrsMut co;
             PadCols pd;
-            if (k > 16) return set_err(GM_ERR_INVALID, "VecVec sumcheck supports at most 16 polynomials");
-            for (int i = 0; i < k; i++) {
-                ci.p[i] = cur[i];
-                co.p[i] = to_a ? bufA[i]->fr() : bufB[i]->fr();
-                pd.v[i] = row_pad[i];
-            }
-            hipLaunchKernelGGL(k_vv_fold, dim3(ceil_div(new_bound, SC_THREADS), (k + 1) / 2), dim3(SC_THREADS), 0, stream, ci, co,
-                               off_cur, off_next, nrows, t, pd, (const Fr*)nullptr, k, coarse_for(off_next), GateArgs{nullptr, 0u, nullptr, 0ull});
+            next_fold(&ci, &co, &pd);
+            hipLaunchKernelGGL(k_vv_fold, dim3(ceil_div(nx_bound, SC_THREADS), (k + 1) / 2), dim3(SC_THREADS), 0, stream, ci, co,
+                               off_cur, nx_off, nrows, t, pd, (const Fr*)nullptr, k, coarse_for(nx_off), GateArgs{nullptr, 0u, nullptr, 0ull});
             GM_LAUNCH_CHECK();
             prof_fold(96.0 * k * (double)(cells_bound / 2));
-            for (int i = 0; i < k; i++) cur[i] = co.p[i];
-            off_cur = off_next;
-            cur_is_a = to_a;
-            started = true;
-            cells_bound = new_bound;
-            { const uint32_t half = cur_max_len / 2; cur_max_len = half + (half & 1); }
-            row_logsize--;
-            multiplier = fr_mul(multiplier, eq_bind_factor(point[binding_var_idx], t));
-            binding_var_idx--;
-            already_bound++;
-            claim_ = evaluate_univar(cached, t);
-            has_cached = false;
-            return GM_OK;
         }
-        return bind_into_dense(t);
+        // the fold's columns and row layout are the current ones now
+        for (int i = 0; i < k; i++) cur[i] = nx_cur[i];
+        off_cur = nx_off;
+        cur_is_a = nx_to_a;
+        started = true;
+        cells_bound = nx_bound;
+        const uint32_t half = cur_max_len / 2;
+        cur_max_len = half + (half & 1);
+        sparse_advance(t);
+        return GM_OK;
+    }
+    // one row variable bound to t
+    void sparse_advance(const Fr& t) {
+        row_logsize--;
+        multiplier = fr_mul(multiplier, eq_bind_factor(point[binding_var_idx], t));
+        binding_var_idx--;
+        already_bound++;
+        claim_ = evaluate_univar(cached, t);
+        has_cached = false;
     }
 
     // vecvec_eq.rs:157-190
@@ -3653,27 +3572,12 @@ struct ScVecVecDeg2 : gm_sc {
         const uint32_t nd_glob = 1u << col_logsize;
         const uint32_t nd = sh.comm ? nrows : nd_glob;  // sharded: the dense columns are this rank's slice of the rows
         std::vector<const Fr*> cptr;
-        ColPtrs ci;
-        ColPtrsMut co;
-        PadCols rp, cpad;
-        for (int i = 0; i < k; i++) {
-            d->owned.emplace_back(new DevBuf());
-            int32_t rc = d->owned.back()->alloc((size_t)nd * sizeof(Fr));
-            if (rc) return rc;
-            ci.p[i] = cur[i];
-            co.p[i] = d->owned.back()->fr();
-            rp.v[i] = row_pad[i];
-            cpad.v[i] = col_pad[i];
-            cptr.push_back(d->owned.back()->fr());
-        }
-        hipLaunchKernelGGL(k_vv_fold_to_dense, dim3(ceil_div(nd, SC_THREADS), k), dim3(SC_THREADS), 0, stream, ci, co,
-                           off_cur, nrows, nd, t, rp, cpad);
-        GM_LAUNCH_CHECK();
-        prof_fold(96.0 * k * (double)nd);
+        int32_t rc = fold_to_dense(t, nd, &d->owned, &cptr);
+        if (rc) return rc;
         // eq over the vertical variables, scaled by the multiplier after this bind (vecvec_eq.rs:177-180)
         const Fr mult = fr_mul(multiplier, eq_bind_factor(point[binding_var_idx], t));
         d->owned.emplace_back(new DevBuf());
-        int32_t rc = d->owned.back()->alloc((size_t)2 * nd_glob * sizeof(Fr));
+        rc = d->owned.back()->alloc((size_t)2 * nd_glob * sizeof(Fr));
         if (rc) return rc;
         Fr* base = d->owned.back()->fr();
         std::vector<Fr*> lv(col_logsize + 1);
@@ -3695,6 +3599,45 @@ struct ScVecVecDeg2 : gm_sc {
     }
 
     int32_t bind_into_dense_deg2(const Fr& t);
+    // the eq-factored dense stage after the bind of the last row variable to t (vecvec_eq.rs:157-190), without its columns
+    std::unique_ptr<ScDenseDeg2> dense_deg2_handover(const Fr& t) const {
+        std::unique_ptr<ScDenseDeg2> d(new ScDenseDeg2());
+        d->stream = stream;
+        d->sp = sp;
+        d->num_vars = col_logsize;
+        d->sh = sh;   // sharded: the columns (or the stage launch) hold this rank's slice of the rows
+        d->loc_vars = col_logsize - sh.lg;
+        d->glob_off = row_base;
+        d->gamma_pows = gamma_pows;
+        d->point.assign(point.begin(), point.begin() + col_logsize);
+        d->multiplier = fr_mul(multiplier, eq_bind_factor(point[binding_var_idx], t));  // vecvec_eq.rs:177-180
+        d->claim_ = evaluate_univar(cached, t);
+        // 1 / (1 - point_j) of the vertical coordinates: already inverted with the row coordinates (a field inversion costs the
+        // host ~15 us; at a hand-over inside the stage kernel every block of the launch is waiting for the next challenge)
+        if (inv_eq0.size() >= col_logsize) d->inv_eq0.assign(inv_eq0.begin(), inv_eq0.begin() + col_logsize);
+        return d;
+    }
+    // the last sparse fold, with t: k dense columns of nd elements, in new buffers appended to *owned, listed in *cols
+    int32_t fold_to_dense(const Fr& t, uint32_t nd, std::vector<std::unique_ptr<DevBuf>>* owned, std::vector<const Fr*>* cols) {
+        ColPtrs ci;
+        ColPtrsMut co;
+        PadCols rp, cpad;
+        for (int i = 0; i < k; i++) {
+            owned->emplace_back(new DevBuf());
+            int32_t rc = owned->back()->alloc((size_t)nd * sizeof(Fr));
+            if (rc) return rc;
+            ci.p[i] = cur[i];
+            co.p[i] = owned->back()->fr();
+            rp.v[i] = row_pad[i];
+            cpad.v[i] = col_pad[i];
+            cols->push_back(co.p[i]);
+        }
+        hipLaunchKernelGGL(k_vv_fold_to_dense, dim3(ceil_div(nd, SC_THREADS), k), dim3(SC_THREADS), 0, stream, ci, co, off_cur, nrows,
+                           nd, t, rp, cpad);
+        GM_LAUNCH_CHECK();
+        prof_fold(96.0 * k * (double)nd);
+        return GM_OK;
+    }
 
     int32_t final_evals(std::vector<Fr>* out) override {
         if (dense2) {
@@ -3711,38 +3654,12 @@ struct ScVecVecDeg2 : gm_sc {
 Fr ScVecVecDeg2::dense2_eq_final() const { return static_cast<const ScDenseDeg2*>(dense2.get())->multiplier; }
 
 int32_t ScVecVecDeg2::bind_into_dense_deg2(const Fr& t) {
-    std::unique_ptr<ScDenseDeg2> d(new ScDenseDeg2());
-    d->stream = stream;
-    d->sp = sp;
-    d->num_vars = col_logsize;
-    d->sh = sh;
-    d->loc_vars = col_logsize - sh.lg;
-    d->glob_off = row_base;
-    d->gamma_pows = gamma_pows;
-    d->point.assign(point.begin(), point.begin() + col_logsize);
-    d->multiplier = fr_mul(multiplier, eq_bind_factor(point[binding_var_idx], t));  // vecvec_eq.rs:177-180
-    d->claim_ = evaluate_univar(cached, t);
-    if (inv_eq0.size() >= col_logsize) d->inv_eq0.assign(inv_eq0.begin(), inv_eq0.begin() + col_logsize);
+    std::unique_ptr<ScDenseDeg2> d = dense_deg2_handover(t);
     const uint32_t nd = sh.comm ? nrows : (1u << col_logsize);  // sharded: this rank's slice of the rows
     std::vector<const Fr*> cptr;
-    ColPtrs ci;
-    ColPtrsMut co;
-    PadCols rp, cpad;
-    for (int i = 0; i < k; i++) {
-        d->owned.emplace_back(new DevBuf());
-        int32_t rc = d->owned.back()->alloc((size_t)nd * sizeof(Fr));
-        if (rc) return rc;
-        ci.p[i] = cur[i];
-        co.p[i] = d->owned.back()->fr();
-        rp.v[i] = row_pad[i];
-        cpad.v[i] = col_pad[i];
-        cptr.push_back(d->owned.back()->fr());
-    }
-    hipLaunchKernelGGL(k_vv_fold_to_dense, dim3(ceil_div(nd, SC_THREADS), k), dim3(SC_THREADS), 0, stream, ci, co, off_cur, nrows,
-                       nd, t, rp, cpad);
-    GM_LAUNCH_CHECK();
-    prof_fold(96.0 * k * (double)nd);
-    int32_t rc = d->cols.init(k, cptr.data(), nd);
+    int32_t rc = fold_to_dense(t, nd, &d->owned, &cptr);
+    if (rc) return rc;
+    rc = d->cols.init(k, cptr.data(), nd);
     if (rc) return rc;
     rc = upload_gamma(gamma_pows, &d->d_gamma, stream);
     if (rc) return rc;

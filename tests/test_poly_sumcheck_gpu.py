@@ -197,3 +197,14 @@ def test_state_errors_mirror_reference_panics():
     so.unipoly()
     with pytest.raises(ffi.GmError):
         so.unipoly()                    # dense_eq.rs:109-111 panic!()
+    # destroyed while the fold of its first round waits in the stream for the challenge: the object releases that gate, and
+    # the next object on the stream runs as usual
+    nv = 4
+    cols = rand_cols(rng, 3, 1 << nv)
+    claim = sum(a * b % F.P * c for a, b, c in zip(*cols)) % F.P
+    so = H.Sumcheckable.dense(1, None, nv, H.cols_to_dev(cols), 0, claim)
+    so.unipoly()
+    so.close()
+    ref = SC.DenseSumcheckObjectSO(cols, SC.Prod3Fn(), nv, claim)
+    gpu = H.Sumcheckable.dense(1, None, nv, H.cols_to_dev(cols), 0, claim)
+    run_rounds(gpu, ref, nv, rng)
