@@ -2,6 +2,7 @@
 // (final MSM recombination).  See include/gkrmsm.h.
 #include "algfn.hip.h"
 #include "common.hpp"
+#include "fnprog.hpp"
 
 using namespace gm;
 
@@ -226,6 +227,15 @@ extern "C" int32_t gm_memcpy_d2d(void* d, const void* sPtr, size_t bytes, void* 
 }
 
 extern "C" int32_t gm_fn_shape(const gm_fn* f, int32_t* n_ins, int32_t* n_outs, int32_t* deg) {
+    if (fn_has_prog(f)) {
+        ProgFn pf;
+        const int32_t rc = prog_fn_parse(f, &pf);
+        if (rc) return rc;
+        if (n_ins) *n_ins = pf.n_ins;
+        if (n_outs) *n_outs = pf.n_outs;
+        if (deg) *deg = pf.deg;
+        return GM_OK;
+    }
     GM_REQUIRE(f && f->nseg >= 1 && f->nseg <= GM_FN_MAX_SEG, "bad gm_fn");
     GmFn g;
     g.nseg = f->nseg;
@@ -267,6 +277,19 @@ extern "C" int32_t gm_fr_host(int32_t op, const uint64_t* h_a, const uint64_t* h
 }
 
 extern "C" int32_t gm_fn_host(const gm_fn* f, const uint64_t* h_in, uint64_t* h_out, uint64_t n) {
+    if (fn_has_prog(f)) {
+        ProgFn pf;
+        const int32_t rc = prog_fn_parse(f, &pf);
+        if (rc) return rc;
+        GM_REQUIRE(h_in && h_out, "null argument");
+        Fr in[GM_MAX_COLS], out[GM_MAX_COLS];
+        for (uint64_t r = 0; r < n; r++) {
+            memcpy(in, h_in + 4 * r * pf.n_ins, 32 * (size_t)pf.n_ins);
+            prog_fn_exec_host(pf, in, out);
+            memcpy(h_out + 4 * r * pf.n_outs, out, 32 * (size_t)pf.n_outs);
+        }
+        return GM_OK;
+    }
     int32_t ni, no, dg;
     int32_t rc = gm_fn_shape(f, &ni, &no, &dg);
     if (rc) return rc;

@@ -8,6 +8,7 @@
 // column): a lane moves whole elements with two 16-byte accesses and consecutive lanes touch consecutive
 // elements, so every wave-level load covers one contiguous 2 KiB span.
 #include "common.hpp"
+#include "fnprog.hpp"
 #include "segfn.hip.h"
 
 namespace gm {
@@ -59,6 +60,26 @@ __global__ void __launch_bounds__(256) k_dense_map_split(SegPlan sp, ColPtrs in,
                 fr_store(out.p[col] + pos, o[q]);
             }
     }
+}
+
+// ---- program functions (fnprog.hpp): the per-row function is prog_eval_row
+__global__ void __launch_bounds__(256) k_dense_map_prog(ProgPlan pp, ColPtrs in, ColPtrsMut out, uint64_t n) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    prog_eval_row(pp, [&](int c) { return fr_load(in.p[c] + i); }, [&](int o, const Fr& v) { fr_store(out.p[o] + i, v); });
+}
+
+// the split of k_dense_map_split
+__global__ void __launch_bounds__(256) k_dense_map_split_prog(ProgPlan pp, ColPtrs in, ColPtrsMut out, uint64_t n, uint32_t lo_bit,
+                                                               uint32_t bundle) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t half = (uint32_t)(i >> lo_bit) & 1u;
+    const uint64_t pos = ((i >> (lo_bit + 1)) << lo_bit) | (i & ((1ull << lo_bit) - 1));
+    prog_eval_row(pp, [&](int c) { return fr_load(in.p[c] + i); }, [&](int o, const Fr& v) {
+        const uint32_t col = 2 * (o / bundle) * bundle + half * bundle + o % bundle;
+        fr_store(out.p[col] + pos, v);
+    });
 }
 
 // out[c][i] = in[c][2i] + t * (in[c][2i+1] - in[c][2i]);  blockIdx.y = column
@@ -125,6 +146,29 @@ int32_t launch_dense_map_split(const SegPlan& sp, const Fr* const* in, Fr* const
 #define GM_LAUNCH_DENSE_MAP_SPLIT(P) hipLaunchKernelGGL(k_dense_map_split<P>, dim3(ceil_div(n, 256)), dim3(256), 0, s, sp, ci, co, n, lo_bit, bundle)
     GM_MAP_DISPATCH(uniform_prim_of(sp), GM_LAUNCH_DENSE_MAP_SPLIT)
 #undef GM_LAUNCH_DENSE_MAP_SPLIT
+    GM_LAUNCH_CHECK();
+    return GM_OK;
+}
+
+int32_t launch_dense_map_prog(const ProgPlan& pp, const Fr* const* in, Fr* const* out, uint64_t n, hipStream_t s) {
+    ColPtrs ci;
+    ColPtrsMut co;
+    for (int i = 0; i < pp.n_ins; i++) ci.p[i] = in[i];
+    for (int i = 0; i < pp.n_outs; i++) co.p[i] = out[i];
+    if (n == 0) return GM_OK;
+    hipLaunchKernelGGL(k_dense_map_prog, dim3(ceil_div(n, 256)), dim3(256), 0, s, pp, ci, co, n);
+    GM_LAUNCH_CHECK();
+    return GM_OK;
+}
+
+int32_t launch_dense_map_split_prog(const ProgPlan& pp, const Fr* const* in, Fr* const* out, uint64_t n, uint32_t lo_bit, uint32_t bundle,
+                                    hipStream_t s) {
+    ColPtrs ci;
+    ColPtrsMut co;
+    for (int i = 0; i < pp.n_ins; i++) ci.p[i] = in[i];
+    for (int i = 0; i < 2 * pp.n_outs; i++) co.p[i] = out[i];
+    if (n == 0) return GM_OK;
+    hipLaunchKernelGGL(k_dense_map_split_prog, dim3(ceil_div(n, 256)), dim3(256), 0, s, pp, ci, co, n, lo_bit, bundle);
     GM_LAUNCH_CHECK();
     return GM_OK;
 }
@@ -346,6 +390,17 @@ int32_t launch_eq_sequence(const Fr& mult, const Fr* pt, uint32_t nvars, Fr* con
 // ------------------------------------------------------------------------------------------- C ABI
 extern "C" int32_t gm_dense_map(const gm_fn* f, const uint64_t* const* d_in, uint64_t* const* d_out, uint64_t len,
                                 void* stream) {
+    ProgFn pf;
+    const int32_t pr = prog_fn_parse(f, &pf);
+    if (pr) return pr;
+    if (pf.nseg) {   // a program function: its own kernel, never a SegPlan
+        GM_REQUIRE(d_in && d_out, "null argument");
+        ProgPlan pp;
+        int32_t rc = prog_plan_build(pf, &pp);
+        if (rc) return rc;
+        return launch_dense_map_prog(pp, reinterpret_cast<const Fr* const*>(d_in), reinterpret_cast<Fr* const*>(d_out), len,
+                                     as_stream(stream));
+    }
     GmFn g;
     int32_t rc = to_gmfn(f, &g);
     if (rc) return rc;
@@ -358,6 +413,20 @@ extern "C" int32_t gm_dense_map(const gm_fn* f, const uint64_t* const* d_in, uin
 
 extern "C" int32_t gm_dense_map_split(const gm_fn* f, const uint64_t* const* d_in, uint64_t* const* d_out,
                                       uint64_t len, uint32_t split_lo_bit, uint32_t bundle, void* stream) {
+    ProgFn pf;
+    const int32_t pr = prog_fn_parse(f, &pf);
+    if (pr) return pr;
+    if (pf.nseg) {
+        GM_REQUIRE(d_in && d_out && bundle >= 1, "bad argument");
+        GM_REQUIRE(2 * pf.n_outs <= GM_MAX_COLS, "too many output columns");
+        GM_REQUIRE((len & (len - 1)) == 0 && (2ull << split_lo_bit) <= len, "len must be a power of two > 2^split_lo_bit");
+        GM_REQUIRE(pf.n_outs % (int)bundle == 0, "n_outs must be a multiple of the bundle size");
+        ProgPlan pp;
+        int32_t rc = prog_plan_build(pf, &pp);
+        if (rc) return rc;
+        return launch_dense_map_split_prog(pp, reinterpret_cast<const Fr* const*>(d_in), reinterpret_cast<Fr* const*>(d_out), len,
+                                           split_lo_bit, bundle, as_stream(stream));
+    }
     GmFn g;
     int32_t rc = to_gmfn(f, &g);
     if (rc) return rc;

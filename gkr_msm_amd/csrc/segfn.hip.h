@@ -33,6 +33,9 @@ struct SegPlan {
 
 // returns false if the function does not fit the static limits
 inline bool seg_plan_build(const GmFn& f, SegPlan* sp) {
+    // built-in ids only: a program id (>= GM_FN_PROG_BASE, fnprog.hpp) cast to int8_t would silently become another primitive
+    for (int s = 0; s < f.nseg; s++)
+        if (f.prim[s] < FN_AFF_L1 || f.prim[s] > FN_LOGUP_LAYER) return false;
     sp->nseg = 0;
     sp->n_ins = fn_n_ins(f);
     sp->n_outs = fn_n_outs(f);

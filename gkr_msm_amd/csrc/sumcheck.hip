@@ -20,6 +20,7 @@
 #include <condition_variable>
 #include <type_traits>
 
+#include "fnprog.hpp"
 #include "internal.hpp"
 #include "ragged.hip.h"
 #include "fr9.hip.h"
@@ -1615,6 +1616,146 @@ __global__ void __launch_bounds__(SC_THREADS) k_round_generic(int kind, SegPlan 
     block_reduce_finish<D>(acc, fc);
 }
 
+// ------------------------------------------------------------------------------------------ program functions (fnprog.hpp)
+// The objects' flat term table: the whole function with gamma folded in (coef * gamma^o) and absolute input columns, expanded from
+// the programs' device copies once per object.  blockIdx.y = segment; thread = (copy, term).
+struct ProgExpandArgs {
+    Fr gp[GM_MAX_COLS];
+    const ProgTerm* src[GM_FN_MAX_SEG];
+    uint32_t n_terms[GM_FN_MAX_SEG], count[GM_FN_MAX_SEG], n_ins[GM_FN_MAX_SEG], n_outs[GM_FN_MAX_SEG];
+    uint32_t in0[GM_FN_MAX_SEG], out0[GM_FN_MAX_SEG], dst0[GM_FN_MAX_SEG];
+};
+__global__ void __launch_bounds__(256) k_prog_expand(ProgExpandArgs a, ProgTerm* __restrict__ dst) {
+    const uint32_t s = blockIdx.y, i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.n_terms[s] * a.count[s]) return;
+    const uint32_t c = i / a.n_terms[s], t = i % a.n_terms[s];
+    const ProgTerm T = a.src[s][t];
+    const uint32_t io = a.in0[s] + c * a.n_ins[s], oc = a.out0[s] + c * a.n_outs[s] + T.out;
+    ProgTerm o;
+    o.coef = fr_mul(T.coef, a.gp[oc]);
+    o.nf = T.nf;
+    o.fpack = 0;
+    for (uint32_t j = 0; j < T.nf; j++) o.fpack |= (((T.fpack >> (8 * j)) & 0xffu) + io) << (8 * j);
+    o.out = oc;
+    o.pad = 0;
+    dst[a.dst0[s] + i] = o;
+}
+
+// sum over the terms [t0, t1) of the flat table at the "1" point (v = p1) and the "2" point (v = 2 p1 - p0) of the pair at cell0
+template <bool P1, bool P2>
+__device__ __forceinline__ void prog_pair_eval(const ProgTerm* __restrict__ tab, uint32_t t0, uint32_t t1, const ColPtrs& cols, uint64_t cell0,
+                                               Fr* A1, Fr* A2) {
+    for (uint32_t t = t0; t < t1; t++) {
+        Fr coef;
+        uint32_t nf, fp;
+        prog_term_load(tab + t, &coef, &nf, &fp);
+        Fr a1 = coef, a2 = coef;
+        for (uint32_t j = 0; j < nf; j++, fp >>= 8) {
+            const Fr* col = cols.p[fp & 0xffu];
+            const Fr p1 = fr_load(col + cell0 + 1);
+            if (P1) a1 = fr_mul(a1, p1);
+            if (P2) a2 = fr_mul(a2, fr_sub(fr_dbl(p1), fr_load(col + cell0)));
+        }
+        if (P1) *A1 = fr_add(*A1, a1);
+        if (P2) *A2 = fr_add(*A2, a2);
+    }
+}
+
+// k_round_deg2<VECVEC, SPLIT> for a program function: the same sums (acc[0] at the "1" point, acc[1] at the "2" point, VecVec:
+// acc[2] the tail weight), the same row search and weights; the layer function is the flat table's term loop.
+// SPLIT = false: one thread per pair, every term at both points.  SPLIT = true: blockIdx.y = 2 * chunk + h, one thread per (pair,
+// chunk of `chunk` terms, point): small rounds are latency bound, so the serial chain per thread is what matters.
+template <bool VECVEC, bool SPLIT>
+__global__ void __launch_bounds__(SC_THREADS) k_round_deg2_prog(const ProgTerm* __restrict__ tab, uint32_t n_terms, uint32_t chunk, ColPtrs cols,
+                                                                 const Fr* __restrict__ eq, uint64_t npairs_dense, VVArgs vv, FinishCtx fc) {
+    constexpr int NACC = VECVEC ? 3 : 2;
+    Fr acc[3] = {fr_zero(), fr_zero(), fr_zero()};
+    if (VECVEC && blockIdx.y == 0) {
+        for (uint32_t r = blockIdx.x * SC_THREADS + threadIdx.x; r < vv.nrows; r += gridDim.x * SC_THREADS) {
+            const uint32_t seg = (vv.off[r + 1] - vv.off[r]) >> 1;
+            acc[2] = fr_add(acc[2], fr_mul(fr_load(vv.row_coef + r), fr_sub(fr_one(), fr_load(vv.eq_prefix + seg))));
+        }
+    }
+    const uint32_t t0 = SPLIT ? (blockIdx.y >> 1) * chunk : 0;
+    const uint32_t t1 = SPLIT ? (t0 + chunk < n_terms ? t0 + chunk : n_terms) : n_terms;
+    const int h = SPLIT ? (int)(blockIdx.y & 1) : 0;
+    const uint64_t npairs = VECVEC ? (uint64_t)(vv.off[vv.nrows] >> 1) : npairs_dense;
+    for (uint64_t base = (uint64_t)blockIdx.x * SC_THREADS; base < npairs; base += (uint64_t)gridDim.x * SC_THREADS) {
+        const uint64_t i = base + threadIdx.x;
+        if (i >= npairs) continue;
+        Fr w;
+        if (VECVEC) {
+            const uint32_t cell0 = (uint32_t)(2 * i);
+            const uint32_t r = vv.coarse ? find_row_coarse(vv.off, vv.nrows, vv.coarse, cell0) : find_row(vv.off, vv.nrows, cell0);
+            w = fr_mul(fr_load(eq + ((cell0 - vv.off[r]) >> 1)), fr_load(vv.row_coef + r));
+        } else {
+            w = fr_load(eq + i);
+        }
+        Fr A1 = fr_zero(), A2 = fr_zero();
+        if (!SPLIT) {
+            prog_pair_eval<true, true>(tab, t0, t1, cols, 2 * i, &A1, &A2);
+            acc[0] = fr_add(acc[0], fr_mul(A1, w));
+            acc[1] = fr_add(acc[1], fr_mul(A2, w));
+        } else if (h == 0) {
+            prog_pair_eval<true, false>(tab, t0, t1, cols, 2 * i, &A1, &A2);
+            acc[0] = fr_add(acc[0], fr_mul(A1, w));
+        } else {
+            prog_pair_eval<false, true>(tab, t0, t1, cols, 2 * i, &A1, &A2);
+            acc[1] = fr_add(acc[1], fr_mul(A2, w));
+        }
+    }
+    block_reduce_finish<NACC>(acc, fc);
+}
+
+// k_round_generic<D, SPLIT> kind 0 (EqWrapper(GammaWrapper(f))) for a program function: the round sums at the points 1 .. D, the eq
+// column last.  D = deg + 1 <= 4.  SPLIT: blockIdx.y = D * chunk + point.
+template <int D, bool SPLIT>
+__global__ void __launch_bounds__(SC_THREADS) k_round_generic_prog(const ProgTerm* __restrict__ tab, uint32_t n_terms, uint32_t chunk,
+                                                                    ColPtrs cols, int ncols, uint64_t npairs, FinishCtx fc) {
+    Fr acc[D];
+#pragma unroll
+    for (int s = 0; s < D; s++) acc[s] = fr_zero();
+    const uint32_t t0 = SPLIT ? (blockIdx.y / D) * chunk : 0;
+    const uint32_t t1 = SPLIT ? (t0 + chunk < n_terms ? t0 + chunk : n_terms) : n_terms;
+    const int s_lo = SPLIT ? (int)(blockIdx.y % D) : 0, s_hi = SPLIT ? s_lo + 1 : D;
+    for (uint64_t i = (uint64_t)blockIdx.x * SC_THREADS + threadIdx.x; i < npairs; i += (uint64_t)gridDim.x * SC_THREADS) {
+        Fr G[D];
+#pragma unroll
+        for (int s = 0; s < D; s++) G[s] = fr_zero();
+        for (uint32_t t = t0; t < t1; t++) {
+            Fr coef;
+            uint32_t nf, fp;
+            prog_term_load(tab + t, &coef, &nf, &fp);
+            Fr a[D];
+#pragma unroll
+            for (int s = 0; s < D; s++) a[s] = coef;
+            for (uint32_t j = 0; j < nf; j++, fp >>= 8) {
+                const Fr* col = cols.p[fp & 0xffu];
+                const Fr p0 = fr_load(col + 2 * i), p1 = fr_load(col + 2 * i + 1);
+                const Fr d = fr_sub(p1, p0);
+                Fr v = p1;   // the value at point s: p1 + (s - 1) d
+#pragma unroll
+                for (int s = 0; s < D; s++) {
+                    if (s) v = fr_add(v, d);
+                    if (s >= s_lo && s < s_hi) a[s] = fr_mul(a[s], v);
+                }
+            }
+#pragma unroll
+            for (int s = 0; s < D; s++)
+                if (s >= s_lo && s < s_hi) G[s] = fr_add(G[s], a[s]);
+        }
+        const Fr e0 = fr_load(cols.p[ncols - 1] + 2 * i), e1 = fr_load(cols.p[ncols - 1] + 2 * i + 1);
+        const Fr ed = fr_sub(e1, e0);
+        Fr e = e1;
+#pragma unroll
+        for (int s = 0; s < D; s++) {
+            if (s) e = fr_add(e, ed);
+            if (s >= s_lo && s < s_hi) acc[s] = fr_add(acc[s], fr_mul(G[s], e));
+        }
+    }
+    block_reduce_finish<D>(acc, fc);
+}
+
 }  // namespace gm
 
 using namespace gm;
@@ -2160,6 +2301,7 @@ struct StageRun {
     }
     // a: geometry, data pointers, eq pointers and pads filled by the caller
     int32_t launch(const SegPlan& sp_in, const ColPtrs& cp, const Fr* d_gamma, StageArgs a, hipStream_t s, bool may_wait = true) {
+        if (sp_in.nseg < 0) return set_err(GM_ERR_STATE, "a program function reached the stage kernel");
         // term split (segfn.hip.h): more, shorter evaluation chains per round when the wider grid still fits the device
         SegPlan sp_split;
         const bool split = seg_plan_split_terms(sp_in, &sp_split) &&
@@ -2477,10 +2619,18 @@ static ScProf& sc_prof() {
     static thread_local ScProf p;
     return p;
 }
+#define PROF_PROG 1024   // first profiler class of the program round kernels (launch_round_deg2_prog)
 static const char* sc_class_name(int cls) {
     // cls = prim * 4 + variant; variant 0: k_round_deg2_lean9x2 dense, 1: k_round_deg2_lean9x2 VecVec (both in rows named
     // k_round_deg2_lean<>), 2: k_round_generic3_lean, 3: k_round_prod3_lean
     static thread_local char buf[64];
+    if (cls >= PROF_PROG) {   // program round kernels (launch_round_deg2_prog, launch_round_generic_prog)
+        const int c = cls - PROF_PROG, kb = c & 3, D = c >> 4;
+        const char* form = (c & 4) ? "split" : "pair";
+        if (kb == 2) snprintf(buf, sizeof(buf), "k_round_generic_prog<%d,%s>", D, form);
+        else snprintf(buf, sizeof(buf), "k_round_deg2_prog<%s,%s>", kb == 1 ? "vecvec" : "dense", form);
+        return buf;
+    }
     const int prim = cls >> 2, var = cls & 3;
     const char* pn = prim == FN_AFF_L1 ? "AFF_L1" : prim == FN_AFF_L2 ? "AFF_L2" : prim == FN_AFF_L3 ? "AFF_L3" : prim == FN_PROJ_L1 ? "PROJ_L1"
                    : prim == FN_PROJ_L2 ? "PROJ_L2" : prim == FN_PROJ_L3 ? "PROJ_L3" : prim == FN_PT_BIT_CHOICE ? "PT_BIT_CHOICE"
@@ -2534,6 +2684,7 @@ static inline void prof_fold(double bytes) {
 // count (VecVec: cb / 2 from the capacity bound cb of the cells; the exact count lives on the device, off[nrows]).
 static int32_t launch_round_deg2(hipStream_t s, const SegPlan& sp, const Fr* const* cols, int k, const Fr* eq, const Fr* gp,
                                  uint64_t npairs, const VVArgs* vv, const FinishCtx& fc) {
+    if (sp.nseg < 0) return set_err(GM_ERR_STATE, "a program function reached the built-in round kernels");
     const VVArgs none{nullptr, 0, nullptr, nullptr, nullptr};
     const VVArgs& va = vv ? *vv : none;
     const uint64_t npairs_dense = vv ? 0 : npairs;
@@ -2576,6 +2727,127 @@ static int32_t launch_round_deg2(hipStream_t s, const SegPlan& sp, const Fr* con
     }
     GM_LAUNCH_CHECK();
     if (!lean || split) prof_small_round(64.0 * k * (double)npairs);
+    return GM_OK;
+}
+
+// ---- program functions: the object's flat term table and its round kernels ------------------------------------------------
+// A program object's SegPlan carries only n_ins / n_outs / deg, and nseg = -1: the built-in dispatch points (launch_round_deg2,
+// StageRun::launch, ScDense's built-in kernels) refuse it, so a program id can never reach k_stage, a lean kernel or prim_exec.
+static bool sp_is_prog(const SegPlan& sp) { return sp.nseg < 0; }
+static SegPlan prog_marker_plan(const ProgFn& pf) {
+    SegPlan sp;
+    memset(&sp, 0, sizeof(sp));
+    sp.nseg = -1; sp.n_ins = pf.n_ins; sp.n_outs = pf.n_outs; sp.deg = pf.deg;
+    return sp;
+}
+struct ProgObj {
+    std::unique_ptr<ProgRef> ref;   // gm_fn_program_destroy returns GM_ERR_STATE while this lives
+    DevBuf table;
+    uint32_t n_terms = 0;
+};
+// the object's layer function on one host row (pads, the host's last rounds)
+static void fn_exec_host(const ProgObj* po, const SegPlan& sp, const Fr* in, Fr* out) {
+    if (po) prog_fn_exec_host(po->ref->fn, in, out);
+    else seg_plan_exec_host(sp, in, out);
+}
+// gp: gamma^o for every output o of the whole function
+static int32_t prog_obj_build(const ProgFn& pf, const std::vector<Fr>& gp, hipStream_t s, std::shared_ptr<ProgObj>* out) {
+    ProgPlan pp;
+    int32_t rc = prog_plan_build(pf, &pp);
+    if (rc) return rc;
+    std::shared_ptr<ProgObj> o(new ProgObj());
+    ProgExpandArgs a;
+    memset(&a, 0, sizeof(a));
+    for (int i = 0; i < pf.n_outs && i < (int)gp.size(); i++) a.gp[i] = gp[i];
+    uint32_t tot = 0, widest = 0;
+    for (int g = 0; g < pf.nseg; g++) {
+        a.src[g] = pp.seg[g].terms;
+        a.n_terms[g] = (uint32_t)pf.prog[g]->terms.size();
+        a.count[g] = (uint32_t)pf.count[g];
+        a.n_ins[g] = (uint32_t)pp.seg[g].n_ins; a.n_outs[g] = (uint32_t)pp.seg[g].n_outs;
+        a.in0[g] = (uint32_t)pp.seg[g].in0; a.out0[g] = (uint32_t)pp.seg[g].out0;
+        a.dst0[g] = tot;
+        tot += a.n_terms[g] * a.count[g];
+        widest = std::max(widest, a.n_terms[g] * a.count[g]);
+    }
+    o->n_terms = tot;
+    rc = o->table.alloc(((size_t)tot + 1) * sizeof(ProgTerm));
+    if (rc) return rc;
+    if (widest) {
+        hipLaunchKernelGGL(k_prog_expand, dim3(ceil_div(widest, 256), pf.nseg), dim3(256), 0, s, a, reinterpret_cast<ProgTerm*>(o->table.p));
+        GM_LAUNCH_CHECK();
+    }
+    o->ref.reset(new ProgRef(pf));
+    *out = o;
+    return GM_OK;
+}
+// terms per split chunk: at most 8 chunks, at least 4 terms each
+static uint32_t prog_chunk(uint32_t n_terms, uint32_t* n_chunks) {
+    uint32_t c = n_terms < 4 ? 4 : ceil_div(n_terms, 8);
+    if (c < 4) c = 4;
+    *n_chunks = n_terms ? ceil_div(n_terms, c) : 1;
+    return c;
+}
+// profiler classes of the program round kernels: PROF_PROG + 16 D + 4 split + (0 deg-2 dense, 1 deg-2 VecVec, 2 generic)
+// launch_round_deg2 for a program object: split form for small rounds, one thread per pair for large ones
+static int32_t launch_round_deg2_prog(hipStream_t s, const ProgObj& po, const Fr* const* cols, int k, const Fr* eq, uint64_t npairs,
+                                      const VVArgs* vv, const FinishCtx& fc) {
+    const VVArgs none{nullptr, 0, nullptr, nullptr, nullptr};
+    const VVArgs& va = vv ? *vv : none;
+    const uint64_t npairs_dense = vv ? 0 : npairs;
+    const uint64_t bound_pairs = vv ? npairs + 1 : npairs;
+    const bool split = bound_pairs <= SC_SPLIT_MAX_PAIRS;
+    uint32_t nch = 1;
+    const uint32_t chunk = prog_chunk(po.n_terms, &nch);
+    const dim3 grid = round_grid(vv && vv->nrows > bound_pairs ? vv->nrows : bound_pairs, split ? 2 * (int)nch : 1);
+    ColPtrs cp;
+    for (int i = 0; i < k; i++) cp.p[i] = cols[i];
+    const ProgTerm* tab = reinterpret_cast<const ProgTerm*>(po.table.p);
+    const int pi = prof_begin(s, PROF_PROG + 16 * 2 + (split ? 4 : 0) + (vv ? 1 : 0), k, npairs, vv ? vv->off + vv->nrows : nullptr,
+                              (int)(2 * po.n_terms * 2 + (vv ? 3 : 2)));
+    if (split) {
+        if (vv) hipLaunchKernelGGL((k_round_deg2_prog<true, true>), grid, dim3(SC_THREADS), 0, s, tab, po.n_terms, chunk, cp, eq, npairs_dense, va, fc);
+        else hipLaunchKernelGGL((k_round_deg2_prog<false, true>), grid, dim3(SC_THREADS), 0, s, tab, po.n_terms, chunk, cp, eq, npairs_dense, va, fc);
+    } else {
+        if (vv) hipLaunchKernelGGL((k_round_deg2_prog<true, false>), grid, dim3(SC_THREADS), 0, s, tab, po.n_terms, po.n_terms, cp, eq, npairs_dense, va, fc);
+        else hipLaunchKernelGGL((k_round_deg2_prog<false, false>), grid, dim3(SC_THREADS), 0, s, tab, po.n_terms, po.n_terms, cp, eq, npairs_dense, va, fc);
+    }
+    prof_end(s, pi);
+    GM_LAUNCH_CHECK();
+    if (split) prof_small_round(64.0 * k * (double)npairs);
+    return GM_OK;
+}
+// the round kernel of a kind-0 ScDense object over a program function (D = deg + 1 points, the eq column last)
+static int32_t launch_round_generic_prog(hipStream_t s, const ProgObj& po, int D, const ColPtrs& cp, int ncols, uint64_t npairs,
+                                         const FinishCtx& fc_in) {
+    const bool split = npairs <= SC_SPLIT_MAX_PAIRS;
+    uint32_t nch = 1;
+    const uint32_t chunk = split ? prog_chunk(po.n_terms, &nch) : po.n_terms;
+    const int ny = split ? D * (int)nch : 1;
+    dim3 grid = round_grid(npairs, ny);
+    FinishCtx fc = fc_in;
+    if (D == 4) {
+        // four sums: the limb accumulators and the pinned report hold three; the stored partials (SC_MAX_BLOCKS x 3 elements) then
+        // bound the grid
+        fc.acc = nullptr;
+        const uint32_t cap = (SC_MAX_BLOCKS * 3 / 4) / (uint32_t)ny;
+        if (grid.x > cap) grid.x = cap;
+    }
+    const ProgTerm* tab = reinterpret_cast<const ProgTerm*>(po.table.p);
+    const int pi = prof_begin(s, PROF_PROG + 16 * D + (split ? 4 : 0) + 2, ncols, npairs, nullptr, (int)(D * (po.n_terms * 2 + 1)));
+#define GM_LAUNCH_GEN_PROG(DD)                                                                                                          \
+    if (split) hipLaunchKernelGGL((k_round_generic_prog<DD, true>), grid, dim3(SC_THREADS), 0, s, tab, po.n_terms, chunk, cp, ncols, npairs, fc); \
+    else hipLaunchKernelGGL((k_round_generic_prog<DD, false>), grid, dim3(SC_THREADS), 0, s, tab, po.n_terms, chunk, cp, ncols, npairs, fc);
+    switch (D) {
+        case 2: GM_LAUNCH_GEN_PROG(2) break;
+        case 3: GM_LAUNCH_GEN_PROG(3) break;
+        case 4: GM_LAUNCH_GEN_PROG(4) break;
+        default: return set_err(GM_ERR_INVALID, "unsupported degree %d", D);
+    }
+#undef GM_LAUNCH_GEN_PROG
+    prof_end(s, pi);
+    GM_LAUNCH_CHECK();
+    if (split) prof_small_round(64.0 * ncols * (double)npairs);
     return GM_OK;
 }
 
@@ -2696,6 +2968,7 @@ static int32_t enqueue_dense_fold(RoundPipe& pipe, RoundScratch& rs, FoldCols& c
 struct ScDense : gm_sc {
     int kind = 0;  // 0: EqWrapper(GammaWrapper(f, gamma)) with the eq column last; 1: Prod3
     SegPlan sp{};
+    std::shared_ptr<ProgObj> prog;   // kind 0 over a program function (sp is then only its marker, sp_is_prog)
     int D = 3;
     uint32_t num_vars = 0, round_idx = 0;
     FoldCols cols;
@@ -2738,6 +3011,13 @@ struct ScDense : gm_sc {
         FinishCtx fc;
         int32_t rc = rs.round_ctx(sh, &fc);
         if (rc) return rc;
+        if (prog) {   // a program function: its own kernel (never the built-in ones below)
+            rc = launch_round_generic_prog(stream, *prog, D, cp, cols.k, npairs, fc);
+            if (rc) return rc;
+            pipe.k_seq[round & 63] = fc.seq;
+            return GM_OK;
+        }
+        if (kind == 0 && sp_is_prog(sp)) return set_err(GM_ERR_STATE, "a program function reached the built-in round kernels");
         const int lean = (kind == 0 && D == 3 && !split && cols.k <= 7) ? lean_prim_of(sp) : 0;
         if (kind == 2) {
             FoldedCols fcols;
@@ -2859,6 +3139,7 @@ struct ScDense : gm_sc {
 // ---- DenseDeg2SumcheckObjectSO (dense_eq.rs:61-173) ---------------------------------------------
 struct ScDenseDeg2 : gm_sc {
     SegPlan sp{};
+    std::shared_ptr<ProgObj> prog;   // a program function (sp is then only its marker): launch_round_deg2_prog, never the stage kernel
     uint32_t num_vars = 0, round_idx = 0;
     FoldCols cols;
     std::vector<Fr> gamma_pows, point;
@@ -2924,7 +3205,8 @@ struct ScDenseDeg2 : gm_sc {
         FinishCtx fc0;
         int32_t rc = rs.round_ctx(sh, &fc0);
         if (rc) return rc;
-        rc = launch_round_deg2(stream, sp, cols.cur.data(), cols.k, eq_cur, d_gamma.fr(), npairs, nullptr, fc0);
+        rc = prog ? launch_round_deg2_prog(stream, *prog, cols.cur.data(), cols.k, eq_cur, npairs, nullptr, fc0)
+                  : launch_round_deg2(stream, sp, cols.cur.data(), cols.k, eq_cur, d_gamma.fr(), npairs, nullptr, fc0);
         if (rc) return rc;
         if (devx) {
             int32_t rc = rs.exchange(sh, 2, stream);
@@ -2958,7 +3240,8 @@ struct ScDenseDeg2 : gm_sc {
     // in the stream when the challenge arrives, ~10 us of launch latency per round)
     int32_t launch_small_round(const ColPtrs& cp, const Fr* eq, uint64_t npairs, uint32_t round) {
         const FinishCtx fc = rs.ctx();
-        int32_t rc = launch_round_deg2(stream, sp, cp.p, cols.k, eq, d_gamma.fr(), npairs, nullptr, fc);
+        int32_t rc = prog ? launch_round_deg2_prog(stream, *prog, cp.p, cols.k, eq, npairs, nullptr, fc)
+                          : launch_round_deg2(stream, sp, cp.p, cols.k, eq, d_gamma.fr(), npairs, nullptr, fc);
         if (rc) return rc;
         pipe.k_seq[round & 63] = fc.seq;
         return GM_OK;
@@ -3051,8 +3334,8 @@ struct ScDenseDeg2 : gm_sc {
                 in1[c] = hcols[c][2 * i + 1];
                 in2[c] = fr_sub(fr_dbl(in1[c]), hcols[c][2 * i]);
             }
-            seg_plan_exec_host(sp, in1, o1);
-            seg_plan_exec_host(sp, in2, o2);
+            fn_exec_host(prog.get(), sp, in1, o1);
+            fn_exec_host(prog.get(), sp, in2, o2);
             Fr a1 = o1[0], a2 = o2[0];
             for (int o = 1; o < sp.n_outs; o++) {
                 a1 = fr_add(a1, fr_mul(gamma_pows[o], o1[o]));
@@ -3096,7 +3379,7 @@ struct ScDenseDeg2 : gm_sc {
         // (a sharded object keeps to pre-enqueued rounds: whether a tail launch runs would have to be agreed between the ranks, as the
         // VecVec object does for its stage; sharded dense objects of the image part are the dense stages of VecVec layers, which
         // are inside that launch already)
-        const bool tail_ok = !tail_denied && !sh.comm && stage_enabled() && sp.nseg <= 32 && rs.pinned_ours();
+        const bool tail_ok = !prog && !tail_denied && !sh.comm && stage_enabled() && sp.nseg <= 32 && rs.pinned_ours();
         if (!tail_active && tail_ok && stage_fits(r, npairs) && pipe.k_enq <= r) {
             int32_t rc = launch_tail(cp, r, npairs);   // the object starts small: everything runs in the tail
             if (rc) return rc;
@@ -3206,6 +3489,7 @@ struct ScDenseDeg2 : gm_sc {
 // ---- VecVecDeg2SumcheckObjectSO (vecvec_eq.rs:72-398) -------------------------------------------
 struct ScVecVecDeg2 : gm_sc {
     SegPlan sp{};
+    std::shared_ptr<ProgObj> prog;   // a program function (sp is then only its marker): never the stage kernel; handed to the dense stage
     GmFn fn{};
     uint32_t nrows = 0, col_logsize = 0, row_logsize = 0;  // row_logsize shrinks with every sparse bind
     uint32_t n_row_vars0 = 0;                               // row variables at creation
@@ -3314,9 +3598,9 @@ struct ScVecVecDeg2 : gm_sc {
         // pads: f(row_pad..) weighted by W, f(col_pad..) by the coefficient tail (vecvec_eq.rs:309-315, 345-371)
         Fr in[GM_MAX_COLS], pr[GM_MAX_COLS], pc[GM_MAX_COLS];
         for (int i = 0; i < k; i++) in[i] = row_pad[i];
-        seg_plan_exec_host(sp, in, pr);
+        fn_exec_host(prog.get(), sp, in, pr);
         for (int i = 0; i < k; i++) in[i] = col_pad[i];
-        seg_plan_exec_host(sp, in, pc);
+        fn_exec_host(prog.get(), sp, in, pc);
         Fr padsum = fr_zero(), colsum = fr_zero();
         for (int o = 0; o < sp.n_outs; o++) {
             padsum = fr_add(padsum, o == 0 ? pr[o] : fr_mul(pr[o], gamma_pows[o]));
@@ -3401,7 +3685,7 @@ struct ScVecVecDeg2 : gm_sc {
     }
     // what every rank sees alike: the shape fits one launch (the geometry is this rank's slice of the rows, the same on every rank)
     bool stage_shape_ok() const {
-        if (!stage_enabled() || RoundScratch::dev_exchange(sh) || k > 16 || col_logsize < 1 || nrows > (1u << col_logsize)) return false;
+        if (prog || !stage_enabled() || RoundScratch::dev_exchange(sh) || k > 16 || col_logsize < 1 || nrows > (1u << col_logsize)) return false;
         const uint32_t nd = sh.comm ? nrows : (1u << col_logsize);
         if (nd < 2 || (nd & (nd - 1)) != 0 || stage_dev_rounds() < 1) return false;
         for (uint32_t i = 0; i < col_logsize; i++)
@@ -3486,7 +3770,8 @@ struct ScVecVecDeg2 : gm_sc {
         FinishCtx fc;
         int32_t rc = rs.round_ctx(sh, &fc);
         if (rc) return rc;
-        rc = launch_round_deg2(stream, sp, cols_now, k, eq_row, d_gamma.fr(), cb / 2, &va, fc);
+        rc = prog ? launch_round_deg2_prog(stream, *prog, cols_now, k, eq_row, cb / 2, &va, fc)
+                  : launch_round_deg2(stream, sp, cols_now, k, eq_row, d_gamma.fr(), cb / 2, &va, fc);
         if (rc) return rc;
         pipe.k_seq[ab & 63] = fc.seq;
         return GM_OK;
@@ -3565,6 +3850,7 @@ struct ScVecVecDeg2 : gm_sc {
         d->stream = stream;
         d->kind = 0;
         d->sp = sp;
+        d->prog = prog;
         d->D = 3;
         d->num_vars = col_logsize;
         d->sh = sh;
@@ -3604,6 +3890,7 @@ struct ScVecVecDeg2 : gm_sc {
         std::unique_ptr<ScDenseDeg2> d(new ScDenseDeg2());
         d->stream = stream;
         d->sp = sp;
+        d->prog = prog;
         d->num_vars = col_logsize;
         d->sh = sh;   // sharded: the columns (or the stage launch) hold this rank's slice of the rows
         d->loc_vars = col_logsize - sh.lg;
@@ -3676,10 +3963,22 @@ int32_t ScVecVecDeg2::bind_into_dense_deg2(const Fr& t) {
 
 // ============================================================================================ C ABI
 static int32_t parse_fn(const gm_fn* f, GmFn* g, SegPlan* sp) {
+    if (fn_has_prog(f)) return set_err(GM_ERR_INVALID, "program function where only built-in ids are accepted");
     int32_t rc = to_gmfn(f, g);
     if (rc) return rc;
     if (!seg_plan_build(*g, sp)) return set_err(GM_ERR_INVALID, "function too wide");
     return GM_OK;
+}
+
+// a program function (pf->nseg >= 1, *sp = its marker plan) or a built-in one (*g, *sp built): the choice is made here, before either plan
+static int32_t parse_any_fn(const gm_fn* f, GmFn* g, SegPlan* sp, ProgFn* pf) {
+    int32_t rc = prog_fn_parse(f, pf);
+    if (rc) return rc;
+    if (pf->nseg) {
+        *sp = prog_marker_plan(*pf);
+        return GM_OK;
+    }
+    return parse_fn(f, g, sp);
 }
 
 static Fr rlc_claims(const std::vector<Fr>& gp, const uint64_t* h_claims, int n) {
@@ -3700,9 +3999,11 @@ extern "C" int32_t gm_sc_dense_deg2_create(const gm_fn* f, uint32_t num_vars, co
     GM_REQUIRE(out && d_cols && h_point && h_gamma && h_claims && num_vars >= 1 && num_vars <= 30, "bad argument");
     std::unique_ptr<ScDenseDeg2> so(new ScDenseDeg2());
     GmFn g;
-    int32_t rc = parse_fn(f, &g, &so->sp);
+    ProgFn pf;
+    int32_t rc = parse_any_fn(f, &g, &so->sp, &pf);
     if (rc) return rc;
     GM_REQUIRE(so->sp.deg == 2, "DenseDeg2Sumcheck needs a degree-2 function (dense_eq.rs:200)");
+    GM_REQUIRE(so->sp.n_ins >= 1, "function without inputs");
     so->stream = as_stream(stream);
     so->num_vars = num_vars;
     so->sh = current_shard();
@@ -3720,6 +4021,11 @@ extern "C" int32_t gm_sc_dense_deg2_create(const gm_fn* f, uint32_t num_vars, co
     if (rc) return rc;
     rc = alloc_gamma(so->gamma_pows, &so->d_gamma);
     if (rc) return rc;
+    if (pf.nseg) {
+        GM_REQUIRE(!so->sh.comm, "sharded objects take built-in functions only");
+        rc = prog_obj_build(pf, so->gamma_pows, so->stream, &so->prog);
+        if (rc) return rc;
+    }
     // eq_poly_sequence(point[0 .. n-1])  (dense_eq.rs:85): levels 0..n-1, level i has 2^i entries
     if (so->sh.comm && so->sh.lg >= 1 && so->loc_vars >= 1) {
         // sharded: this rank's slice of the levels lg .. n-1 (local levels 0 .. loc_vars-1, scaled by eq(point[0..lg), rank)) and the
@@ -3764,7 +4070,8 @@ extern "C" int32_t gm_sc_vecvec_deg2_create(const gm_fn* f, const gm_vv* polys, 
                                             void* stream) {
     GM_REQUIRE(out && polys && h_point && h_gamma && h_claims, "bad argument");
     std::unique_ptr<ScVecVecDeg2> so(new ScVecVecDeg2());
-    int32_t rc = parse_fn(f, &so->fn, &so->sp);
+    ProgFn pf;
+    int32_t rc = parse_any_fn(f, &so->fn, &so->sp, &pf);
     if (rc) return rc;
     GM_REQUIRE(so->sp.deg == 2, "VecVecDeg2Sumcheck needs a degree-2 function (vecvec_eq.rs:426)");
     GM_REQUIRE((int)polys->k == so->sp.n_ins, "%u polys for a %d-input function", polys->k, so->sp.n_ins);
@@ -3828,6 +4135,11 @@ extern "C" int32_t gm_sc_vecvec_deg2_create(const gm_fn* f, const gm_vv* polys, 
     }
     rc = alloc_gamma(so->gamma_pows, &so->d_gamma);   // stored by the eq-table launch below
     if (rc) return rc;
+    if (pf.nseg) {
+        GM_REQUIRE(!so->sh.comm, "sharded objects take built-in functions only");
+        rc = prog_obj_build(pf, so->gamma_pows, s, &so->prog);
+        if (rc) return rc;
+    }
     // EQPolyData::new (vecvec.rs:85-119)
     uint32_t max_seg_log = 0;
     {   // liblasso log_2: exact for powers of two, else bit length
@@ -3916,17 +4228,24 @@ extern "C" int32_t gm_sc_dense_create(int32_t kind, const gm_fn* f, uint32_t num
     so->num_vars = num_vars;
     int ncols = 3;
     std::vector<Fr> gp = {fr_one()};
+    ProgFn pf;
     if (kind == 0) {
         GM_REQUIRE(h_gamma, "gamma required");
         GmFn g;
-        int32_t rc = parse_fn(f, &g, &so->sp);
+        int32_t rc = parse_any_fn(f, &g, &so->sp, &pf);
         if (rc) return rc;
         GM_REQUIRE(so->sp.n_outs > 1, "GammaWrapper needs n_outs > 1 (sumcheck.rs:714)");
+        if (pf.nseg) {
+            GM_REQUIRE(pf.deg >= 1 && pf.deg <= 3, "kind 0 takes program functions of degree 1 .. 3 (got %d)", pf.deg);
+            GM_REQUIRE(pf.n_ins + 1 <= GM_MAX_COLS, "kind 0: %d inputs + the eq column exceed %d columns", pf.n_ins, GM_MAX_COLS);
+        }
         so->D = so->sp.deg + 1;
         ncols = so->sp.n_ins + 1;
         Fr gamma;
         memcpy(&gamma, h_gamma, 32);
         gp = make_gamma_pows(gamma, so->sp.n_outs);
+    } else if (fn_has_prog(f)) {
+        return set_err(GM_ERR_INVALID, "kind %d does not take program functions", kind);
     } else if (kind == 2) {
         // FoldedProdAlgFn(gamma, nargs) (multiopen_reduction.rs:13-42): f = IdAlgFn(nargs) only carries nargs
         GM_REQUIRE(h_gamma && f && f->nseg == 1 && f->count[0] >= 1 && f->count[0] <= 8, "kind 2 needs gamma and f = {GM_FN_ID x nargs}, nargs <= 8");
@@ -3939,7 +4258,7 @@ extern "C" int32_t gm_sc_dense_create(int32_t kind, const gm_fn* f, uint32_t num
     } else {
         so->D = 3;
     }
-    GM_REQUIRE(so->D == 2 || so->D == 3, "unsupported degree %d", so->D);
+    GM_REQUIRE(so->D == 2 || so->D == 3 || (pf.nseg && so->D == 4), "unsupported degree %d", so->D);
     memcpy(&so->claim_, h_claim, 32);
     so->sh = current_shard();
     GM_REQUIRE(so->sh.lg <= num_vars, "more ranks than elements");
@@ -3948,6 +4267,11 @@ extern "C" int32_t gm_sc_dense_create(int32_t kind, const gm_fn* f, uint32_t num
     if (rc) return rc;
     rc = upload_gamma(gp, &so->d_gamma, so->stream);
     if (rc) return rc;
+    if (pf.nseg) {
+        GM_REQUIRE(!so->sh.comm, "sharded objects take built-in functions only");
+        rc = prog_obj_build(pf, gp, so->stream, &so->prog);
+        if (rc) return rc;
+    }
     rc = so->rs.init(so->stream);
     if (rc) return rc;
     *out = so.release();

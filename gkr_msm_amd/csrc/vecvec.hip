@@ -10,6 +10,7 @@
 //
 // Layout: rows back to back, off[r] = first cell of row r, every stored row length is even; the k columns
 // are separate arrays over the same cells, so one offsets table and one binary search serve all of them.
+#include "fnprog.hpp"
 #include "internal.hpp"
 #include "msm_plan.hpp"
 #include "ragged.hip.h"
@@ -139,6 +140,63 @@ __global__ void __launch_bounds__(256) k_vv_map_split_to_dense(SegPlan sp, ColPt
     }
 }
 
+// ---- program functions (fnprog.hpp): the kernels above with prog_eval_row as the per-row function
+__global__ void __launch_bounds__(256) k_vv_map_prog(ProgPlan pp, ColPtrs in, ColPtrsMut out, uint64_t total) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= total) return;
+    prog_eval_row(pp, [&](int c) { return fr_load(in.p[c] + i); }, [&](int o, const Fr& v) { fr_store(out.p[o] + i, v); });
+}
+
+__global__ void __launch_bounds__(256) k_vv_map_split_prog(ProgPlan pp, ColPtrs in, ColPtrsMut out, const uint32_t* __restrict__ off_in,
+                                                            const uint32_t* __restrict__ off_out, uint32_t nrows, uint32_t bundle, PadVals pad,
+                                                            const uint32_t* __restrict__ coarse_out) {
+    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= off_out[nrows]) return;
+    const uint32_t r = coarse_out ? find_row_coarse(off_out, nrows, coarse_out, j) : find_row(off_out, nrows, j);
+    const uint32_t p = j - off_out[r];
+    const uint32_t in0 = off_in[r], half_len = (off_in[r + 1] - in0) >> 1;
+    if (p < half_len) {
+        for (uint32_t h = 0; h < 2; h++) {
+            const uint64_t src = (uint64_t)in0 + 2 * p + h;
+            prog_eval_row(pp, [&](int c) { return fr_load(in.p[c] + src); }, [&](int oc, const Fr& v) {
+                const uint32_t col = 2 * (oc / bundle) * bundle + h * bundle + oc % bundle;
+                fr_store(out.p[col] + j, v);
+            });
+        }
+    } else {
+        for (int oc = 0; oc < pp.n_outs; oc++)
+            for (uint32_t h = 0; h < 2; h++) {
+                const uint32_t col = 2 * (oc / bundle) * bundle + h * bundle + oc % bundle;
+                fr_store(out.p[col] + j, pad.v[oc]);
+            }
+    }
+}
+
+__global__ void __launch_bounds__(256) k_vv_map_split_to_dense_prog(ProgPlan pp, ColPtrs in, ColPtrsMut out, const uint32_t* __restrict__ off_in,
+                                                                     uint32_t nrows, uint32_t nrows_dense, uint32_t bundle, PadVals row_pad,
+                                                                     PadVals col_pad) {
+    const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= nrows_dense) return;
+    const bool stored = r < nrows;
+    const uint32_t in0 = stored ? off_in[r] : 0;
+    const uint32_t len = stored ? off_in[r + 1] - in0 : 0;
+    if (len) {
+        for (uint32_t h = 0; h < 2; h++)
+            prog_eval_row(pp, [&](int c) { return fr_load(in.p[c] + in0 + h); }, [&](int oc, const Fr& v) {
+                const uint32_t col = 2 * (oc / bundle) * bundle + h * bundle + oc % bundle;
+                fr_store(out.p[col] + r, v);
+            });
+    } else {
+        // (one array per branch: a select between the two kernel-argument arrays by a run-time index would copy them to scratch)
+        for (int oc = 0; oc < pp.n_outs; oc++)
+            for (uint32_t h = 0; h < 2; h++) {
+                const uint32_t col = 2 * (oc / bundle) * bundle + h * bundle + oc % bundle;
+                if (stored) fr_store(out.p[col] + r, row_pad.v[oc]);
+                else fr_store(out.p[col] + r, col_pad.v[oc]);
+            }
+    }
+}
+
 __global__ void __launch_bounds__(256) k_vv_to_dense(ColPtrs in, ColPtrsMut out, const uint32_t* __restrict__ off,
                                                       uint32_t nrows, uint32_t row_logsize, uint64_t n_dense,
                                                       PadVals row_pad, PadVals col_pad) {
@@ -186,14 +244,27 @@ int32_t gm_vv::alloc_cols(uint32_t k_, uint64_t total_) {
     return GM_OK;
 }
 
-static void pads_through(const SegPlan& sp, const gm_vv* in, std::vector<Fr>* rp, std::vector<Fr>* cp) {
+// the per-row function of a VecVec map: a built-in plan, or a program function (its host form and its device plan)
+struct VvFn {
+    const SegPlan* sp = nullptr;
+    const ProgFn* pf = nullptr;
+    const ProgPlan* pp = nullptr;
+    int n_ins() const { return sp ? sp->n_ins : pp->n_ins; }
+    int n_outs() const { return sp ? sp->n_outs : pp->n_outs; }
+    void exec_host(const Fr* a, Fr* o) const {
+        if (sp) seg_plan_exec_host(*sp, a, o);
+        else prog_fn_exec_host(*pf, a, o);
+    }
+};
+
+static void pads_through(const VvFn& f, const gm_vv* in, std::vector<Fr>* rp, std::vector<Fr>* cp) {
     Fr a[GM_MAX_COLS], o[GM_MAX_COLS];
-    for (int i = 0; i < sp.n_ins; i++) a[i] = in->row_pad[i];
-    seg_plan_exec_host(sp, a, o);
-    rp->assign(o, o + sp.n_outs);
-    for (int i = 0; i < sp.n_ins; i++) a[i] = in->col_pad[i];
-    seg_plan_exec_host(sp, a, o);
-    cp->assign(o, o + sp.n_outs);
+    for (int i = 0; i < f.n_ins(); i++) a[i] = in->row_pad[i];
+    f.exec_host(a, o);
+    rp->assign(o, o + f.n_outs());
+    for (int i = 0; i < f.n_ins(); i++) a[i] = in->col_pad[i];
+    f.exec_host(a, o);
+    cp->assign(o, o + f.n_outs());
 }
 
 namespace gm {
@@ -225,24 +296,28 @@ static std::shared_ptr<DevBuf> off_view(const std::shared_ptr<DevBuf>& base, uin
     return v;
 }
 
-int32_t vv_map(const SegPlan& sp, const gm_vv* in, gm_vv** out, hipStream_t s) {
+static int32_t vv_map_fn(const VvFn& f, const gm_vv* in, gm_vv** out, hipStream_t s) {
     // exec reads args[0..n_ins): extra trailing polys are ignored, as in the reference
     // (bintree level 0 maps affine l1 over the 6-poly GlueSplit output, bintree_add.rs:213-215)
-    GM_REQUIRE((int)in->k >= sp.n_ins, "vecvec_map: %u polys for a %d-input function", in->k, sp.n_ins);
+    GM_REQUIRE((int)in->k >= f.n_ins(), "vecvec_map: %u polys for a %d-input function", in->k, f.n_ins());
     std::unique_ptr<gm_vv> o(new gm_vv());
     o->nrows = in->nrows; o->row_logsize = in->row_logsize; o->col_logsize = in->col_logsize;
     o->max_row_len = in->max_row_len;
     o->row_base = in->row_base; o->sharded = in->sharded;
     o->off = in->off;  // shared shape
     o->share_levels(in, 0);
-    int32_t rc = o->alloc_cols(sp.n_outs, in->total);
+    int32_t rc = o->alloc_cols(f.n_outs(), in->total);
     if (rc) return rc;
-    pads_through(sp, in, &o->row_pad, &o->col_pad);
+    pads_through(f, in, &o->row_pad, &o->col_pad);
     ColPtrs ci;
     ColPtrsMut co;
-    for (int i = 0; i < sp.n_ins; i++) ci.p[i] = in->cols[i]->fr();
-    for (int i = 0; i < sp.n_outs; i++) co.p[i] = o->cols[i]->fr();
-    if (in->total) {
+    for (int i = 0; i < f.n_ins(); i++) ci.p[i] = in->cols[i]->fr();
+    for (int i = 0; i < f.n_outs(); i++) co.p[i] = o->cols[i]->fr();
+    if (in->total && f.pp) {
+        hipLaunchKernelGGL(k_vv_map_prog, dim3(ceil_div(in->total, 256)), dim3(256), 0, s, *f.pp, ci, co, in->total);
+        GM_LAUNCH_CHECK();
+    } else if (in->total) {
+        const SegPlan& sp = *f.sp;
 #define GM_LAUNCH_VV_MAP(P) hipLaunchKernelGGL(k_vv_map<P>, dim3(ceil_div(in->total, 256)), dim3(256), 0, s, sp, ci, co, in->total)
         GM_MAP_DISPATCH(uniform_prim_of(sp), GM_LAUNCH_VV_MAP)
 #undef GM_LAUNCH_VV_MAP
@@ -251,13 +326,19 @@ int32_t vv_map(const SegPlan& sp, const gm_vv* in, gm_vv** out, hipStream_t s) {
     *out = o.release();
     return GM_OK;
 }
+int32_t vv_map(const SegPlan& sp, const gm_vv* in, gm_vv** out, hipStream_t s) {
+    VvFn f;
+    f.sp = &sp;
+    return vv_map_fn(f, in, out, s);
+}
 
 static inline uint32_t pad2(uint32_t v) { return v + (v & 1u); }
 
-int32_t vv_map_split(const SegPlan& sp, const gm_vv* in, uint32_t bundle, gm_vv** out, hipStream_t s) {
-    GM_REQUIRE((int)in->k == sp.n_ins, "vecvec_map_split: %u polys for a %d-input function", in->k, sp.n_ins);
+static int32_t vv_map_split_fn(const VvFn& f, const gm_vv* in, uint32_t bundle, gm_vv** out, hipStream_t s) {
+    const int n_ins = f.n_ins(), n_outs = f.n_outs();
+    GM_REQUIRE((int)in->k == n_ins, "vecvec_map_split: %u polys for a %d-input function", in->k, n_ins);
     GM_REQUIRE(in->row_logsize >= 1, "cannot split row_logsize 0");
-    GM_REQUIRE(bundle >= 1 && sp.n_outs % (int)bundle == 0 && sp.n_outs <= GM_VV_MAX_OUTS, "bad bundle / width");
+    GM_REQUIRE(bundle >= 1 && n_outs % (int)bundle == 0 && n_outs <= GM_VV_MAX_OUTS, "bad bundle / width");
     std::unique_ptr<gm_vv> o(new gm_vv());
     o->nrows = in->nrows; o->row_logsize = in->row_logsize - 1; o->col_logsize = in->col_logsize;
     o->max_row_len = pad2(in->max_row_len / 2);
@@ -281,12 +362,12 @@ int32_t vv_map_split(const SegPlan& sp, const gm_vv* in, uint32_t bundle, gm_vv*
         GM_HIP(hipMemcpyAsync(&tot, off_out + in->nrows, 4, hipMemcpyDeviceToHost, s));
         GM_HIP(hipStreamSynchronize(s));
     }
-    rc = o->alloc_cols(2 * sp.n_outs, tot);
+    rc = o->alloc_cols(2 * n_outs, tot);
     if (rc) return rc;
     std::vector<Fr> rp, cp;
-    pads_through(sp, in, &rp, &cp);
+    pads_through(f, in, &rp, &cp);
     PadVals pv;
-    for (int oc = 0; oc < sp.n_outs; oc++) {
+    for (int oc = 0; oc < n_outs; oc++) {
         pv.v[oc] = rp[oc];
         for (uint32_t h = 0; h < 2; h++) {
             const uint32_t col = 2 * (oc / bundle) * bundle + h * bundle + oc % bundle;
@@ -296,11 +377,20 @@ int32_t vv_map_split(const SegPlan& sp, const gm_vv* in, uint32_t bundle, gm_vv*
     }
     ColPtrs ci;
     ColPtrsMut co;
-    for (int i = 0; i < sp.n_ins; i++) ci.p[i] = in->cols[i]->fr();
-    for (int i = 0; i < 2 * sp.n_outs; i++) co.p[i] = o->cols[i]->fr();
+    for (int i = 0; i < n_ins; i++) ci.p[i] = in->cols[i]->fr();
+    for (int i = 0; i < 2 * n_outs; i++) co.p[i] = o->cols[i]->fr();
     if (tot) {
         const uint32_t* coarse_tab = (o->coarse && o->coarse_off && o->off_level < o->coarse_off->size())
                                          ? reinterpret_cast<const uint32_t*>(o->coarse->p) + (*o->coarse_off)[o->off_level] : (const uint32_t*)nullptr;
+        if (f.pp) {
+            hipLaunchKernelGGL(k_vv_map_split_prog, dim3(ceil_div(tot, 256)), dim3(256), 0, s, *f.pp, ci, co,
+                               reinterpret_cast<const uint32_t*>(in->off->p), reinterpret_cast<const uint32_t*>(o->off->p), in->nrows, bundle, pv,
+                               coarse_tab);
+            GM_LAUNCH_CHECK();
+            *out = o.release();
+            return GM_OK;
+        }
+        const SegPlan& sp = *f.sp;
 #define GM_LAUNCH_VV_MAP_SPLIT(P)                                                                                             \
     hipLaunchKernelGGL(k_vv_map_split<P>, dim3(ceil_div(tot, 256)), dim3(256), 0, s, sp, ci, co,                                 \
                        reinterpret_cast<const uint32_t*>(in->off->p), reinterpret_cast<const uint32_t*>(o->off->p), in->nrows, bundle, pv, coarse_tab)
@@ -312,22 +402,45 @@ int32_t vv_map_split(const SegPlan& sp, const gm_vv* in, uint32_t bundle, gm_vv*
     return GM_OK;
 }
 
-int32_t vv_map_split_to_dense(const SegPlan& sp, const gm_vv* in, uint32_t bundle, Fr* const* d_out, hipStream_t s) {
-    GM_REQUIRE((int)in->k == sp.n_ins, "vecvec_map_split_to_dense: %u polys for a %d-input function", in->k, sp.n_ins);
+static int32_t vv_map_split_to_dense_fn(const VvFn& f, const gm_vv* in, uint32_t bundle, Fr* const* d_out, hipStream_t s) {
+    const int n_ins = f.n_ins(), n_outs = f.n_outs();
+    GM_REQUIRE((int)in->k == n_ins, "vecvec_map_split_to_dense: %u polys for a %d-input function", in->k, n_ins);
     GM_REQUIRE(in->row_logsize == 1, "row_logsize must be 1 (vecvec.rs:618)");
-    GM_REQUIRE(bundle >= 1 && sp.n_outs % (int)bundle == 0 && sp.n_outs <= GM_VV_MAX_OUTS, "bad bundle / width");
+    GM_REQUIRE(bundle >= 1 && n_outs % (int)bundle == 0 && n_outs <= GM_VV_MAX_OUTS, "bad bundle / width");
     std::vector<Fr> rp, cp;
-    pads_through(sp, in, &rp, &cp);
+    pads_through(f, in, &rp, &cp);
     PadVals prow, pcol;
-    for (int oc = 0; oc < sp.n_outs; oc++) { prow.v[oc] = rp[oc]; pcol.v[oc] = cp[oc]; }
+    for (int oc = 0; oc < n_outs; oc++) { prow.v[oc] = rp[oc]; pcol.v[oc] = cp[oc]; }
     ColPtrs ci;
     ColPtrsMut co;
-    for (int i = 0; i < sp.n_ins; i++) ci.p[i] = in->cols[i]->fr();
-    for (int i = 0; i < 2 * sp.n_outs; i++) co.p[i] = d_out[i];
+    for (int i = 0; i < n_ins; i++) ci.p[i] = in->cols[i]->fr();
+    for (int i = 0; i < 2 * n_outs; i++) co.p[i] = d_out[i];
     const uint32_t nd = in->sharded ? in->nrows : (1u << in->col_logsize);  // sharded: this rank's rows only
-    hipLaunchKernelGGL(k_vv_map_split_to_dense, dim3(ceil_div(nd, 256)), dim3(256), 0, s, sp, ci, co,
-                       reinterpret_cast<const uint32_t*>(in->off->p), in->nrows, nd, bundle, prow, pcol);
+    if (f.pp)
+        hipLaunchKernelGGL(k_vv_map_split_to_dense_prog, dim3(ceil_div(nd, 256)), dim3(256), 0, s, *f.pp, ci, co,
+                           reinterpret_cast<const uint32_t*>(in->off->p), in->nrows, nd, bundle, prow, pcol);
+    else
+        hipLaunchKernelGGL(k_vv_map_split_to_dense, dim3(ceil_div(nd, 256)), dim3(256), 0, s, *f.sp, ci, co,
+                           reinterpret_cast<const uint32_t*>(in->off->p), in->nrows, nd, bundle, prow, pcol);
     GM_LAUNCH_CHECK();
+    return GM_OK;
+}
+int32_t vv_map_split(const SegPlan& sp, const gm_vv* in, uint32_t bundle, gm_vv** out, hipStream_t s) {
+    VvFn f;
+    f.sp = &sp;
+    return vv_map_split_fn(f, in, bundle, out, s);
+}
+int32_t vv_map_split_to_dense(const SegPlan& sp, const gm_vv* in, uint32_t bundle, Fr* const* d_out, hipStream_t s) {
+    VvFn f;
+    f.sp = &sp;
+    return vv_map_split_to_dense_fn(f, in, bundle, d_out, s);
+}
+// a program function: its host form (pads) and its device plan
+static int32_t vv_prog_fn(const ProgFn& pf, ProgPlan* pp, VvFn* f) {
+    int32_t rc = prog_plan_build(pf, pp);
+    if (rc) return rc;
+    f->pf = &pf;
+    f->pp = pp;
     return GM_OK;
 }
 
@@ -476,6 +589,18 @@ int32_t gm::vv_from_msm(const gm_msm_plan* p, const uint64_t* d_points_xy, uint3
 
 extern "C" int32_t gm_vv_map(const gm_fn* f, const gm_vv* in, gm_vv** out, void* stream) {
     GM_REQUIRE(in && out, "null argument");
+    {
+        ProgFn pf;
+        const int32_t pr = prog_fn_parse(f, &pf);
+        if (pr) return pr;
+        if (pf.nseg) {   // a program function: its own kernel, never a SegPlan
+            ProgPlan pp;
+            VvFn vf;
+            int32_t rc = vv_prog_fn(pf, &pp, &vf);
+            if (rc) return rc;
+            return vv_map_fn(vf, in, out, as_stream(stream));
+        }
+    }
     GmFn g;
     int32_t rc = to_gmfn(f, &g);
     if (rc) return rc;
@@ -486,6 +611,18 @@ extern "C" int32_t gm_vv_map(const gm_fn* f, const gm_vv* in, gm_vv** out, void*
 
 extern "C" int32_t gm_vv_map_split(const gm_fn* f, const gm_vv* in, uint32_t bundle, gm_vv** out, void* stream) {
     GM_REQUIRE(in && out, "null argument");
+    {
+        ProgFn pf;
+        const int32_t pr = prog_fn_parse(f, &pf);
+        if (pr) return pr;
+        if (pf.nseg) {   // a program function: its own kernel, never a SegPlan
+            ProgPlan pp;
+            VvFn vf;
+            int32_t rc = vv_prog_fn(pf, &pp, &vf);
+            if (rc) return rc;
+            return vv_map_split_fn(vf, in, bundle, out, as_stream(stream));
+        }
+    }
     GmFn g;
     int32_t rc = to_gmfn(f, &g);
     if (rc) return rc;
@@ -497,6 +634,18 @@ extern "C" int32_t gm_vv_map_split(const gm_fn* f, const gm_vv* in, uint32_t bun
 extern "C" int32_t gm_vv_map_split_to_dense(const gm_fn* f, const gm_vv* in, uint32_t bundle, uint64_t* const* d_out,
                                             void* stream) {
     GM_REQUIRE(in && d_out, "null argument");
+    {
+        ProgFn pf;
+        const int32_t pr = prog_fn_parse(f, &pf);
+        if (pr) return pr;
+        if (pf.nseg) {   // a program function: its own kernel, never a SegPlan
+            ProgPlan pp;
+            VvFn vf;
+            int32_t rc = vv_prog_fn(pf, &pp, &vf);
+            if (rc) return rc;
+            return vv_map_split_to_dense_fn(vf, in, bundle, reinterpret_cast<Fr* const*>(d_out), as_stream(stream));
+        }
+    }
     GmFn g;
     int32_t rc = to_gmfn(f, &g);
     if (rc) return rc;

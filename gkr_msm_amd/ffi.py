@@ -32,6 +32,18 @@ def make_fn(*segs):
     return f
 
 
+FN_PROG_BASE, FN_PROG_MAX_DEG, FN_PROG_MAX_TERMS = 4096, 4, 1024
+
+
+class GmFnTerm(C.Structure):
+    """gm_fn_term: coef (Montgomery limbs) * prod in[factor[j]] added to output `out`"""
+    _fields_ = [("coef", C.c_uint64 * 4), ("out", C.c_uint16), ("n_factors", C.c_uint8), ("reserved", C.c_uint8),
+                ("factor", C.c_uint8 * 4)]
+
+
+assert C.sizeof(GmFnTerm) == 40
+
+
 _lib = None
 
 u64p = C.POINTER(C.c_uint64)
@@ -109,6 +121,8 @@ _SIGS = {
     "gm_memcpy_d2h": (C.c_int32, [vp, vp, C.c_size_t, vp]),
     "gm_memcpy_d2d": (C.c_int32, [vp, vp, C.c_size_t, vp]),
     "gm_fn_shape": (C.c_int32, [C.POINTER(GmFn), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "gm_fn_program_create": (C.c_int32, [C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(GmFnTerm), C.c_uint32, C.POINTER(C.c_int32)]),
+    "gm_fn_program_destroy": (C.c_int32, [C.c_int32]),
     "gm_fr_batch": (C.c_int32, [C.c_int32, vp, vp, vp, C.c_uint64, vp]),
     "gm_fr_host": (C.c_int32, [C.c_int32, vp, vp, vp, C.c_uint64]),
     "gm_fn_host": (C.c_int32, [C.POINTER(GmFn), vp, vp, C.c_uint64]),

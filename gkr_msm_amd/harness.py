@@ -1028,3 +1028,28 @@ def sc_profile_read():
     out = [dict(kernel=r.kernel.decode(), launches=r.launches, k_cols=r.k_cols, total_ms=r.total_ms, max_ms=r.max_ms, pairs=r.pairs,
                 alg_bytes=r.alg_bytes, fr_mul=r.fr_mul, max_ms_pairs=r.max_ms_pairs) for r in rows[: n.value]]
     return out, orb.value, fb.value
+
+
+def fn_terms(terms):
+    """[(coef, out, (factor, ...)), ...] (coef a field element as an int) -> a ctypes array of gm_fn_term"""
+    arr = (ffi.GmFnTerm * max(len(terms), 1))()
+    for i, (coef, out, factors) in enumerate(terms):
+        limbs = codec.to_mont_limbs([coef % codec.P])[0]
+        for l in range(4):
+            arr[i].coef[l] = int(limbs[l])
+        arr[i].out = out
+        arr[i].n_factors = len(factors)
+        for j, f in enumerate(factors):
+            arr[i].factor[j] = f
+    return arr
+
+
+def make_program(n_ins, n_outs, deg, terms):
+    """gm_fn_program_create over [(coef, out, (factor, ...)), ...] -> the program id (use it in ffi.make_fn((id, count), ...))"""
+    pid = C.c_int32()
+    ffi.check(ffi.lib().gm_fn_program_create(n_ins, n_outs, deg, fn_terms(terms), len(terms), C.byref(pid)))
+    return pid.value
+
+
+def destroy_program(pid):
+    ffi.check(ffi.lib().gm_fn_program_destroy(pid))

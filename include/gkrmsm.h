@@ -80,7 +80,7 @@ int32_t gm_memcpy_d2d(void* d_dst, const void* d_src, size_t bytes, void* stream
 
 /* ---------------------------------------------------------------- AlgFn descriptors
  * Replaces the Rust generics `Fun: AlgFn<F>` (src/cleanup/utils/algfn.rs:21-34).  A function is a
- * left-to-right stack of up to 4 segments (primitive id, repeat count):
+ * left-to-right stack of up to 4 segments (primitive id or program id, repeat count):
  *   StackedAlgFn::new(f1, RepeatedAlgFn::new(f2, n))  ==  nseg=2, prim={f1,f2}, count={1,n}
  * Primitive ids: twisted_edwards_ops.rs:150-156 plus algfn.rs Id/BitCheck and gen-1 pt_bit_choice. */
 #define GM_FN_AFF_L1 1   /* affine_twisted_edwards_add_l1   (deg 2, 4 -> 3)  */
@@ -104,6 +104,36 @@ typedef struct gm_fn {
 } gm_fn;
 
 int32_t gm_fn_shape(const gm_fn* f, int32_t* n_ins, int32_t* n_outs, int32_t* deg);
+
+/* Caller-defined functions ("programs"): the runtime AlgFn of the reference, ArcedAlgFn::new(f, n_ins, n_outs, deg)
+ * (src/cleanup/utils/algfn.rs:93-131), given as a polynomial in monomial form:
+ *   out[o] = sum over the terms with term.out == o of coef * prod_{j < n_factors} in[factor[j]]
+ * (an output with no terms is 0; duplicate terms add up; a repeated factor is a power).  gm_fn_program_create registers
+ * it (host only: no GPU is touched) and returns an id >= GM_FN_PROG_BASE that goes into gm_fn.prim like a primitive id,
+ * with any repeat count, stacked with other programs.  A gm_fn mixing program and built-in segments is refused
+ * (GM_ERR_INVALID).  `deg` is the declared degree: >= the largest n_factors, <= GM_FN_PROG_MAX_DEG; gm_fn_shape reports
+ * it and the sumcheck objects take their number of evaluation points from it.  Limits: 1 <= n_ins, n_outs <= 64,
+ * n_terms <= GM_FN_PROG_MAX_TERMS, factor indices < n_ins, out < n_outs, reserved == 0.
+ * Program functions run on the device in gm_dense_map, gm_dense_map_split, gm_vv_map, gm_vv_map_split,
+ * gm_vv_map_split_to_dense, gm_sc_dense_deg2_create / gm_sc_vecvec_deg2_create (deg 2) and gm_sc_dense_create kind 0
+ * (deg 1 .. 3); on the host in gm_fn_host.  The whole-protocol drivers keep their built-in layers.
+ * Lifetime: each device receives its own copy of the term table on first use.  A sumcheck object holds a reference:
+ * gm_fn_program_destroy returns GM_ERR_STATE while one exists.  Otherwise it synchronises every device holding a copy
+ * (maps are asynchronous) and frees them; call it from a thread that has no sumcheck round waiting for a challenge.
+ * An unknown or destroyed id is GM_ERR_INVALID everywhere; ids are not reused within a process. */
+#define GM_FN_PROG_BASE 4096   /* program ids are >= this; built-in ids stay < 64 */
+#define GM_FN_PROG_MAX_DEG 4
+#define GM_FN_PROG_MAX_TERMS 1024
+typedef struct gm_fn_term {
+    uint64_t coef[4];                      /* field element, ABI form (Montgomery) */
+    uint16_t out;                          /* output index, < n_outs */
+    uint8_t n_factors;                     /* 0 .. GM_FN_PROG_MAX_DEG; 0 = constant term */
+    uint8_t reserved;                      /* must be 0 */
+    uint8_t factor[GM_FN_PROG_MAX_DEG];    /* input indices < n_ins; repeats allowed (x^2) */
+} gm_fn_term;                              /* 40 bytes */
+int32_t gm_fn_program_create(uint32_t n_ins, uint32_t n_outs, uint32_t deg, const gm_fn_term* terms, uint32_t n_terms,
+                             int32_t* prim_id);
+int32_t gm_fn_program_destroy(int32_t prim_id);
 
 /* ---------------------------------------------------------------- field batch ops (a1)
  * Elementwise Fr arithmetic over device arrays; replaces ark-ff operator calls inside the
