@@ -13,11 +13,14 @@ N > 1 : the path shards by MSM window: rank g owns windows [g*32/N, 
         `weak` (x_logsize = 20 + log2 N: 2^25 bucket cells per rank, as at N = 1) and `config_d` (BASELINE.json configs[3]:
         x_logsize=24, windows sharded N ways), plus the window/row-sharded image-part prover's rounds/sec.
 
-One JSON line on rank 0 (see README / DESIGN.md for the field meanings).  `roofline` is for the dominant MSM kernel (level-0
-bucket add, k_add_level0) and `sumcheck.roofline` for the dominant round kernel of the prover, both timed with HIP events on
-the launch stream inside the timed runs; `cpu_baseline` is the C oracle (oracle/gkrmsm_oracle*.c, OpenMP) on this host,
-rank 0, N = 1 only.  `--dump-outputs DIR` writes what the last timed step returned (dump_outputs); the inputs are seeded, so two
-builds run with the same arguments can be compared file for file.
+One JSON line on rank 0 (see README / DESIGN.md for the field meanings).  A plain run sets up, warms up, times the steps, writes
+--dump-outputs and prints the headline line: `value`, `ms_per_step`, the configuration and the transport.  Everything else is
+measured with `--full` only: `roofline` / `roofline_levels_ge1` / `stage_ms` / `whole_msm` of the MSM, the sumcheck, gen-1, G1 and
+whole-prover legs, the CPU baselines and in-run parity checks and, for N > 1, `n1_same_run`, `weak`, `config_d` and the sharded
+provers.  `roofline` is for the dominant MSM kernel (level-0 bucket add, k_add_level0) and `sumcheck.roofline` for the dominant
+round kernel of the prover, both timed with HIP events on the launch stream inside the timed runs; `cpu_baseline` is the C oracle
+(oracle/gkrmsm_oracle*.c, OpenMP) on this host, rank 0, N = 1 only.  `--dump-outputs DIR` writes what the last timed step returned
+(dump_outputs); the inputs are seeded, so two builds run with the same arguments can be compared file for file.
 """
 import argparse
 import ctypes as C
@@ -211,6 +214,9 @@ def main():
     ap.add_argument("--x-logsize", type=int, default=None)
     ap.add_argument("--d-logsize", type=int, default=8)
     ap.add_argument("--nbits", type=int, default=256)
+    ap.add_argument("--full", action="store_true", help="after the headline, every other leg: MSM stage breakdown and rooflines, "
+                    "sumcheck / gen-1 / G1 / whole-prover figures, CPU baselines and parity checks, N > 1 extra shapes and sharded "
+                    "provers (the options below narrow it)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-threads", type=int, default=0, help="threads of the CPU port (0 = every usable hardware thread; the MSM leg "
                     "cannot use more than its windows, as the reference's rayon loop over windows)")
@@ -440,105 +446,106 @@ def main():
         for pl in plans[1:]:
             pl.close()
         del plans, recv
-        # stage breakdown (one extra, untimed pass)
-        ffi.check(L.gm_msm_profile(plan.h, 2))
-        step()
-        ffi.check(L.gm_msm_profile_read(plan.h, prof, 7))
-        # ("add_level0" / "add_levels_ge1" keep their names: with levels 0 and 1 fused -- the default, see roofline.kernel -- the first
-        # is the fused launch and the second the levels from 2 on)
-        stages = dict(zip(["digits", "histogram", "chunk_scan_offsets", "scatter", "add_level0", "add_levels_ge1", "triangle"],
-                          [round(float(v), 4) for v in prof]))
-        ffi.check(L.gm_msm_profile(plan.h, 0))
         ms_per_step = dt / steps * 1e3
-        dom = float(np.mean(dom_ms)) if dom_ms and dom_ms[0] > 0 else None
-        # algorithmic bytes of one k_add_level0 launch: per output cell 2 gathered affine points (2 x 64 B), 2 cell indices
-        # (2 x 4 B), one projective point written (96 B); cells = windows * N / 2.  Field multiplications: 8 per level-0 add,
-        # 12 per add above (shared sub-products; the layer-by-layer evaluation needs 9 / 13).
-        cells0 = wpr * n // 2
-        fr_mul_step = cells0 * 8 + (cells0 - (wpr << d_log)) * 12 if cells0 > (wpr << d_log) else cells0 * 8
-        fz = C.c_int32(0)
-        ffi.check(L.gm_msm_run_info(plan.h, C.byref(fz)))
-        fused = bool(fz.value)
-        try:
-            cells = (C.c_uint64 * (x_log + 1))()
-            ffi.check(L.gm_msm_level_cells(plan.h, cells, x_log + 1, harness.cur_stream()))
-            adds = [int(cells[l]) // 2 for l in range(1, x_log)]     # adds[0] = additions of level 1, ...
-        except Exception:
-            adds = []
-        if fused and adds:
-            # k_add_level01: bintree levels 0 and 1 in one launch.  Algorithmic bytes per launch (SURVEY 8(d) units): every level-0 addition
-            # gathers two affine points (2 x 64 B) and two cell indices (2 x 4 B); the level-0 cells never exist; every level-1 cell is one
-            # projective point written (96 B; 108 as stored, in the 9 x 29 cell form).  8 field multiplications per level-0 addition, 12 per
-            # level-1 addition.
-            dom_name = "k_add_level01 (bintree levels 0 + 1 fused)"
-            alg_bytes = cells0 * (128 + 8) + int(cells[2]) * 96
-            fr_mul0 = cells0 * 8 + adds[0] * 12
-            first_ge = 2
-            traffic_dom = PMC_TRAFFIC_SC_B.get("k_add_level01")
-            traffic_rest = PMC_TRAFFIC_SC_B.get("k_add_levels_ge2_per_step")
-        else:
+        res = {"x_logsize": x_log, "value": round(n * steps / dt, 1), "ms_per_step": round(ms_per_step, 4),
+               "per_rank_ms_per_step": per_rank_ms, "pipeline_depth": depth, "result_x": hex(result[0])}
+        if args.full:
+            # stage breakdown (one extra, untimed pass)
+            ffi.check(L.gm_msm_profile(plan.h, 2))
+            step()
+            ffi.check(L.gm_msm_profile_read(plan.h, prof, 7))
+            # ("add_level0" / "add_levels_ge1" keep their names: with levels 0 and 1 fused -- the default, see roofline.kernel -- the first
+            # is the fused launch and the second the levels from 2 on)
+            stages = dict(zip(["digits", "histogram", "chunk_scan_offsets", "scatter", "add_level0", "add_levels_ge1", "triangle"],
+                              [round(float(v), 4) for v in prof]))
+            ffi.check(L.gm_msm_profile(plan.h, 0))
+            dom = float(np.mean(dom_ms)) if dom_ms and dom_ms[0] > 0 else None
             # algorithmic bytes of one k_add_level0 launch: per output cell 2 gathered affine points (2 x 64 B), 2 cell indices
             # (2 x 4 B), one projective point written (96 B); cells = windows * N / 2.  Field multiplications: 8 per level-0 add,
             # 12 per add above (shared sub-products; the layer-by-layer evaluation needs 9 / 13).
-            dom_name = "k_add_level0"
-            alg_bytes = cells0 * (128 + 8 + 96)
-            fr_mul0 = cells0 * 8
-            first_ge = 1
-            traffic_dom = PMC_TRAFFIC_MSM_B
-            traffic_rest = PMC_TRAFFIC_GE1_B
-        roofline = None
-        if dom:
-            ach = alg_bytes / (dom * 1e-3) / 1e9
-            roofline = {"bound": "hbm", "kernel": dom_name, "achieved": round(ach, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                        "frac": round(ach / HBM_PEAK_GBS, 4),
-                        "traffic": traffic_dom if (x_log, d_log, nbits, wpr) == (20, 8, 256, 32) else None,
-                        "traffic_note": "PMC bytes per launch = (FETCH_SIZE x %s + WRITE_SIZE) x 1024: this kernel's reads are 64-byte gathers, for which "
-                                        "FETCH_SIZE reads the bytes exactly (profiles/r04/fetch_size_gather_factors.json: factor 1.00-1.06; the x 2 of "
-                                        "the guide is for 16 B / lane coalesced streams)" % PMC_FETCH_FACTOR_GATHER,
-                        "avg_launch_ms": round(dom, 4), "algorithmic_bytes_per_launch": alg_bytes, "fr_mul_per_launch": fr_mul0,
-                        "fr_mul_per_s": round(fr_mul0 / (dom * 1e-3), 1),
-                        "valu_frac_of_measured_ceiling": round(fr_mul0 / (dom * 1e-3) / FR9_MUL_CEILING, 3)}
-            # In the timed loop the kernel shares the chip with the late, latency-bound levels of the previous step (other
-            # stream): that overlap shortens the step and lengthens this launch.  The same launch with the chip to itself
-            # (the untimed stage-breakdown pass below):
-            alone = stages["add_level0"]
-            if alone > 0:
-                roofline["unoverlapped"] = {"launch_ms": alone, "achieved": round(alg_bytes / (alone * 1e-3) / 1e9, 1),
-                                            "frac": round(alg_bytes / (alone * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
-                                            "fr_mul_per_s": round(fr_mul0 / (alone * 1e-3), 1),
-                                            "valu_frac_of_measured_ceiling": round(fr_mul0 / (alone * 1e-3) / FR9_MUL_CEILING, 3)}
-        # the level kernels above (k_add_level on the flat levels, k_add_tail on the late ones), summed over their launches of one step.
-        # Algorithmic bytes per addition as SURVEY 8(d): two projective points read (2 x 96 B), one written (96 B); 12 field
-        # multiplications.  Exact pair counts from the row layouts of the run.
-        roofline_ge1 = None
-        try:
-            rest = adds[first_ge - 1:]
-            t_ge1 = stages["add_levels_ge1"]
-            if t_ge1 > 0 and rest:
-                tot_adds = sum(rest)
-                b_ge1 = tot_adds * 288
-                m_ge1 = tot_adds * 12
-                ach1 = b_ge1 / (t_ge1 * 1e-3) / 1e9
-                roofline_ge1 = {"bound": "hbm", "kernel": "k_add_level (levels %d..) + k_add_tail (the late levels, to %d)" % (first_ge, x_log - 1),
-                                "achieved": round(ach1, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(ach1 / HBM_PEAK_GBS, 4),
-                                "traffic": traffic_rest if (x_log, d_log, nbits, wpr) == (20, 8, 256, 32) else None,
-                                "ms_per_step": round(t_ge1, 4), "additions_per_step": tot_adds, "algorithmic_bytes_per_step": b_ge1,
-                                "fr_mul_per_step": m_ge1, "fr_mul_per_s": round(m_ge1 / (t_ge1 * 1e-3), 1),
-                                "valu_frac_of_measured_ceiling": round(m_ge1 / (t_ge1 * 1e-3) / FR9_MUL_CEILING, 3),
-                                "largest_levels_additions": rest[:4],
-                                "note": "unoverlapped (the untimed stage-breakdown pass); flat launches up to level x - d - 3, one k_add_tail for the rest"}
-        except Exception as e:
-            roofline_ge1 = {"error": repr(e)[:200]}
-        res = {"x_logsize": x_log, "value": round(n * steps / dt, 1), "ms_per_step": round(ms_per_step, 4), "roofline_levels_ge1": roofline_ge1,
-               "per_rank_ms_per_step": per_rank_ms, "pipeline_depth": depth, "roofline": roofline,
-               "stage_ms": stages, "result_x": hex(result[0]),
-               # SURVEY 8(d)'s whole-MSM unit: 96 B of compulsory HBM traffic per point (64 B point + 32 B scalar)
-               "whole_msm": {"algorithmic_bytes_per_point": 96, "achieved_GBps": round(96 * n / (ms_per_step * 1e-3) / 1e9, 2),
-                             "frac_of_hbm_peak": round(96 * n / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS, 5),
-                             "fr_mul_per_step_per_gpu": fr_mul_step,
-                             "fr_mul_per_s_per_gpu": round(fr_mul_step / (ms_per_step * 1e-3), 1),
-                             "valu_frac_of_measured_ceiling": round(fr_mul_step / (ms_per_step * 1e-3) / FR9_MUL_CEILING, 3),
-                             "bound": "integer VALU (8-12 Fr multiplications per bucket add; MFMA not applicable)"}}
+            cells0 = wpr * n // 2
+            fr_mul_step = cells0 * 8 + (cells0 - (wpr << d_log)) * 12 if cells0 > (wpr << d_log) else cells0 * 8
+            fz = C.c_int32(0)
+            ffi.check(L.gm_msm_run_info(plan.h, C.byref(fz)))
+            fused = bool(fz.value)
+            try:
+                cells = (C.c_uint64 * (x_log + 1))()
+                ffi.check(L.gm_msm_level_cells(plan.h, cells, x_log + 1, harness.cur_stream()))
+                adds = [int(cells[l]) // 2 for l in range(1, x_log)]     # adds[0] = additions of level 1, ...
+            except Exception:
+                adds = []
+            if fused and adds:
+                # k_add_level01: bintree levels 0 and 1 in one launch.  Algorithmic bytes per launch (SURVEY 8(d) units): every level-0 addition
+                # gathers two affine points (2 x 64 B) and two cell indices (2 x 4 B); the level-0 cells never exist; every level-1 cell is one
+                # projective point written (96 B; 108 as stored, in the 9 x 29 cell form).  8 field multiplications per level-0 addition, 12 per
+                # level-1 addition.
+                dom_name = "k_add_level01 (bintree levels 0 + 1 fused)"
+                alg_bytes = cells0 * (128 + 8) + int(cells[2]) * 96
+                fr_mul0 = cells0 * 8 + adds[0] * 12
+                first_ge = 2
+                traffic_dom = PMC_TRAFFIC_SC_B.get("k_add_level01")
+                traffic_rest = PMC_TRAFFIC_SC_B.get("k_add_levels_ge2_per_step")
+            else:
+                # algorithmic bytes of one k_add_level0 launch: per output cell 2 gathered affine points (2 x 64 B), 2 cell indices
+                # (2 x 4 B), one projective point written (96 B); cells = windows * N / 2.  Field multiplications: 8 per level-0 add,
+                # 12 per add above (shared sub-products; the layer-by-layer evaluation needs 9 / 13).
+                dom_name = "k_add_level0"
+                alg_bytes = cells0 * (128 + 8 + 96)
+                fr_mul0 = cells0 * 8
+                first_ge = 1
+                traffic_dom = PMC_TRAFFIC_MSM_B
+                traffic_rest = PMC_TRAFFIC_GE1_B
+            roofline = None
+            if dom:
+                ach = alg_bytes / (dom * 1e-3) / 1e9
+                roofline = {"bound": "hbm", "kernel": dom_name, "achieved": round(ach, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                            "frac": round(ach / HBM_PEAK_GBS, 4),
+                            "traffic": traffic_dom if (x_log, d_log, nbits, wpr) == (20, 8, 256, 32) else None,
+                            "traffic_note": "PMC bytes per launch = (FETCH_SIZE x %s + WRITE_SIZE) x 1024: this kernel's reads are 64-byte gathers, for which "
+                                            "FETCH_SIZE reads the bytes exactly (profiles/r04/fetch_size_gather_factors.json: factor 1.00-1.06; the x 2 of "
+                                            "the guide is for 16 B / lane coalesced streams)" % PMC_FETCH_FACTOR_GATHER,
+                            "avg_launch_ms": round(dom, 4), "algorithmic_bytes_per_launch": alg_bytes, "fr_mul_per_launch": fr_mul0,
+                            "fr_mul_per_s": round(fr_mul0 / (dom * 1e-3), 1),
+                            "valu_frac_of_measured_ceiling": round(fr_mul0 / (dom * 1e-3) / FR9_MUL_CEILING, 3)}
+                # In the timed loop the kernel shares the chip with the late, latency-bound levels of the previous step (other
+                # stream): that overlap shortens the step and lengthens this launch.  The same launch with the chip to itself
+                # (the untimed stage-breakdown pass below):
+                alone = stages["add_level0"]
+                if alone > 0:
+                    roofline["unoverlapped"] = {"launch_ms": alone, "achieved": round(alg_bytes / (alone * 1e-3) / 1e9, 1),
+                                                "frac": round(alg_bytes / (alone * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
+                                                "fr_mul_per_s": round(fr_mul0 / (alone * 1e-3), 1),
+                                                "valu_frac_of_measured_ceiling": round(fr_mul0 / (alone * 1e-3) / FR9_MUL_CEILING, 3)}
+            # the level kernels above (k_add_level on the flat levels, k_add_tail on the late ones), summed over their launches of one step.
+            # Algorithmic bytes per addition as SURVEY 8(d): two projective points read (2 x 96 B), one written (96 B); 12 field
+            # multiplications.  Exact pair counts from the row layouts of the run.
+            roofline_ge1 = None
+            try:
+                rest = adds[first_ge - 1:]
+                t_ge1 = stages["add_levels_ge1"]
+                if t_ge1 > 0 and rest:
+                    tot_adds = sum(rest)
+                    b_ge1 = tot_adds * 288
+                    m_ge1 = tot_adds * 12
+                    ach1 = b_ge1 / (t_ge1 * 1e-3) / 1e9
+                    roofline_ge1 = {"bound": "hbm", "kernel": "k_add_level (levels %d..) + k_add_tail (the late levels, to %d)" % (first_ge, x_log - 1),
+                                    "achieved": round(ach1, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(ach1 / HBM_PEAK_GBS, 4),
+                                    "traffic": traffic_rest if (x_log, d_log, nbits, wpr) == (20, 8, 256, 32) else None,
+                                    "ms_per_step": round(t_ge1, 4), "additions_per_step": tot_adds, "algorithmic_bytes_per_step": b_ge1,
+                                    "fr_mul_per_step": m_ge1, "fr_mul_per_s": round(m_ge1 / (t_ge1 * 1e-3), 1),
+                                    "valu_frac_of_measured_ceiling": round(m_ge1 / (t_ge1 * 1e-3) / FR9_MUL_CEILING, 3),
+                                    "largest_levels_additions": rest[:4],
+                                    "note": "unoverlapped (the untimed stage-breakdown pass); flat launches up to level x - d - 3, one k_add_tail for the rest"}
+            except Exception as e:
+                roofline_ge1 = {"error": repr(e)[:200]}
+            res.update({"roofline_levels_ge1": roofline_ge1, "roofline": roofline, "stage_ms": stages,
+                        # SURVEY 8(d)'s whole-MSM unit: 96 B of compulsory HBM traffic per point (64 B point + 32 B scalar)
+                        "whole_msm": {"algorithmic_bytes_per_point": 96, "achieved_GBps": round(96 * n / (ms_per_step * 1e-3) / 1e9, 2),
+                                      "frac_of_hbm_peak": round(96 * n / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS, 5),
+                                      "fr_mul_per_step_per_gpu": fr_mul_step,
+                                      "fr_mul_per_s_per_gpu": round(fr_mul_step / (ms_per_step * 1e-3), 1),
+                                      "valu_frac_of_measured_ceiling": round(fr_mul_step / (ms_per_step * 1e-3) / FR9_MUL_CEILING, 3),
+                                      "bound": "integer VALU (8-12 Fr multiplications per bucket add; MFMA not applicable)"}})
         if bcast_ms is not None:
             res["operand_broadcast_ms"] = round(bcast_ms, 2)
             res["operand_bytes"] = n * 96
@@ -564,11 +571,10 @@ def main():
         "config": {"workload": "pippenger_msm x_logsize=%d d_logsize=%d nbits=%d (bandersnatch, %d windows)" % (
             x_log, d_log, nbits, y_size), "x_logsize": x_log, "d_logsize": d_log, "nbits": nbits,
             "windows_per_gpu": wpr, "sharding": "windows" if world > 1 else "none", "transport": transport},
-        "roofline": main_res["roofline"], "roofline_levels_ge1": main_res["roofline_levels_ge1"], "stage_ms": main_res["stage_ms"],
         "result_x": main_res["result_x"],
-        "whole_msm": main_res["whole_msm"],
     }
-    for k in ("operand_broadcast_ms", "operand_bytes", "per_rank_ms_per_step", "pipeline_depth"):
+    for k in ("roofline", "roofline_levels_ge1", "stage_ms", "whole_msm", "operand_broadcast_ms", "operand_bytes", "per_rank_ms_per_step",
+              "pipeline_depth"):
         if k in main_res:
             out[k] = main_res[k]
     if world == 1 and rccl_seen:
@@ -576,6 +582,7 @@ def main():
     if world > 1:
         out["rccl_ranks_seen"] = rccl_seen["ranks"] if rccl_seen else 0
         out["rccl_distinct_devices"] = rccl_seen["distinct_devices"] if rccl_seen else 0
+    if world > 1 and args.full:
         # the N = 1 figure of the SAME run: every rank runs the whole unsharded MSM on its own GPU (replicas, no exchange)
         try:
             solo = msm_leg(x_main, args.steps, args.warmup, solo=True)
@@ -586,7 +593,7 @@ def main():
             out["n1_same_run"] = {"error": repr(e)[:300]}
 
     # ---- second headline: sumcheck rounds/sec of the image-part prover (triangle + bintree GKR) at the same config
-    if world == 1 and not args.no_sumcheck:
+    if world == 1 and args.full and not args.no_sumcheck:
         y_log = (y_size - 1).bit_length()
         torch.cuda.synchronize()
         t1 = time.perf_counter()
@@ -768,7 +775,7 @@ def main():
             torch.cuda.empty_cache()
 
     # ---- N > 1: the other named shapes in the same line (weak: fixed work per GPU; config D: x_logsize = 24)
-    if world > 1 and not args.no_extra_shapes:
+    if world > 1 and args.full and not args.no_extra_shapes:
         plan.close()
         del d_pts, d_sc
         L.gm_release_cached_memory()
@@ -794,7 +801,7 @@ def main():
     # ---- N > 1: the same prover sharded by windows / bucket rows: per-round all-gather of the partial sums
     # It runs LAST and under a watchdog: it has only been rehearsed with ranks sharing the builder's one-GPU box; if it stalls on a
     # real node the MSM line -- the metric -- must still come out.
-    if world > 1 and not args.no_sumcheck:
+    if world > 1 and args.full and not args.no_sumcheck:
         import threading
 
         def _emit_without_prover():
@@ -1007,7 +1014,7 @@ def main():
         torch.cuda.set_stream(torch.cuda.default_stream())
 
     # ---- gen-1 prover (gkr_msm_simple.rs gkr_msm_prove, Fr part): BASELINE.json configs[2]
-    if world == 1 and not args.no_sumcheck and args.gen1_log_points > 0:
+    if world == 1 and args.full and not args.no_sumcheck and args.gen1_log_points > 0:
         plan.close()
         plan = None
         L.gm_release_cached_memory()
@@ -1140,7 +1147,7 @@ def main():
         torch.cuda.empty_cache()
 
     # ---- BLS12-381 G1 side: KZG-commit-shaped MSM and the outer buckets of PushForwardState::new
-    if world == 1 and args.g1_log_points > 0:
+    if world == 1 and args.full and args.g1_log_points > 0:
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
         ng = 1 << args.g1_log_points
         d_srs = harness.g1_gen_points(ng, 0x53525331)
@@ -1370,7 +1377,7 @@ def main():
         ffi.check(L.gm_g1_release_scratch())
 
     # ---- CPU baseline + in-run parity (rank 0, N = 1)
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.full and not args.no_cpu_baseline:
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
         import oracle_ffi as O
         L.gm_release_cached_memory()

@@ -100,7 +100,7 @@ for k, v in per_launch.items():
         table["k_round_deg2_lean<%s,%s>" % (PRIM.get(int(a), a), "vecvec" if b.strip() == "true" else "dense")] = v
     elif k in ("k_add_level0", "k_add_level01"):
         table[k] = v
-# all launches of the level kernels above level 0 of ONE step: the MSM PMC run is `bench.py --steps 3 --warmup 1` = 3 timed + 1 warm-up
+# all launches of the level kernels above level 0 of ONE step: the MSM PMC run is `bench.py --full --steps 3 --warmup 1` = 3 timed + 1 warm-up
 # + 2 pipeline-priming + 1 stage-breakdown step = 7 steps (bench.py msm_leg)
 ge1 = 0.0
 for k in ("k_add_level", "k_add_tail"):

@@ -29,3 +29,10 @@ def test_dump_outputs_hold_the_step_results_exactly(tmp_path):
 def test_steps_below_one_are_refused():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=300)
     assert r.returncode == 2 and "--steps must be at least 1" in r.stderr
+
+
+def test_full_is_an_option_of_its_own():
+    # --full is parsed like any other option (an unknown one would fail with argparse's own message before the --steps check)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "0"], capture_output=True, text=True,
+                       timeout=300)
+    assert r.returncode == 2 and "--steps must be at least 1" in r.stderr
