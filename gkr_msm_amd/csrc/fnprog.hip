@@ -169,7 +169,7 @@ extern "C" int32_t gm_fn_program_destroy(int32_t prim_id) {
         auto it = R.progs.find(prim_id);
         GM_REQUIRE(it != R.progs.end(), "unknown or destroyed program id %d", prim_id);
         if (it->second->live > 0)
-            return set_err(GM_ERR_STATE, "program %d is held by %d sumcheck object(s): destroy them first", prim_id, it->second->live);
+            return set_err(GM_ERR_STATE, "program %d is held by %d sumcheck object(s) or circuit witness(es): destroy them first", prim_id, it->second->live);
         P = it->second;
         R.progs.erase(it);
     }

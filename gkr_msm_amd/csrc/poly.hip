@@ -106,6 +106,31 @@ __global__ void k_set1(Fr* dst, Fr v) {
     if (threadIdx.x == 0 && blockIdx.x == 0) fr_store(dst, v);
 }
 
+// ---- multilinear evaluation (gm_dense_evaluate)
+#define GM_EVAL_LG 3   // variables one pass folds: a thread reads 2^3 elements and writes one
+struct EvalPt {
+    Fr r[GM_EVAL_LG];   // the coordinates of one pass, in fold order
+};
+
+// One pass folds the LG HIGHEST remaining variables: thread i reads elements i + m n_out (m < 2^LG) of column blockIdx.y -- every
+// load of a wave contiguous -- folds them in registers (m's bit 0 first, with r[0]) and writes out[y][i].  Every Fr operation returns
+// the canonical representative, so the result is the same field element in the same bits as any other fold order (the lowest
+// variable first, as gm_dense_bind does).  No LDS, no barrier: the next pass folds the partials.
+template <int LG>
+__global__ void __launch_bounds__(256) k_dense_eval(ColPtrs in, ColPtrsMut out, uint64_t n_out, EvalPt pt) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_out) return;
+    const Fr* src = in.p[blockIdx.y] + i;
+    Fr v[1 << LG];
+#pragma unroll
+    for (int m = 0; m < (1 << LG); m++) v[m] = fr_load(src + (uint64_t)m * n_out);
+#pragma unroll
+    for (int l = 0; l < LG; l++)
+#pragma unroll
+        for (int m = 0; m < (1 << (LG - l - 1)); m++) v[m] = fr_add(v[2 * m], fr_mul(pt.r[l], fr_sub(v[2 * m + 1], v[2 * m])));
+    fr_store(out.p[blockIdx.y] + i, v[0]);
+}
+
 }  // namespace gm
 
 using namespace gm;
@@ -184,6 +209,47 @@ int32_t launch_dense_fold(const Fr* const* in, Fr* const* out, int k, uint64_t n
         GM_LAUNCH_CHECK();
     }
     return GM_OK;
+}
+
+// evaluate_poly of k columns of 2^nvars elements at pt (pt[0] = MSB) into h_out (host): passes of k_dense_eval, each folding up to
+// GM_EVAL_LG of the highest remaining variables, partials ping-ponging between two scratch buffers; the last pass leaves k elements
+int32_t launch_dense_evaluate(const Fr* const* cols, int k, uint32_t nvars, const Fr* pt, Fr* h_out, hipStream_t s) {
+    if (k == 0) return GM_OK;
+    std::vector<const Fr*> cur(cols, cols + k);
+    DevBuf scratch[2];
+    uint32_t rem = nvars;
+    for (int pass = 0;; pass++) {
+        const uint32_t lg = rem < GM_EVAL_LG ? rem : GM_EVAL_LG;
+        const uint64_t n_out = 1ull << (rem - lg);
+        DevBuf& sb = scratch[pass & 1];
+        if (!sb.p) {
+            int32_t rc = sb.alloc((size_t)k * n_out * sizeof(Fr));   // the largest this buffer will hold: partials only shrink
+            if (rc) return rc;
+        }
+        EvalPt ep;   // the remaining polynomial has the coordinates pt[nvars - rem ..]; this pass binds the first lg of them
+        for (uint32_t l = 0; l < lg; l++) ep.r[l] = pt[nvars - rem + lg - 1 - l];
+        std::vector<const Fr*> nxt(k);
+        for (int c = 0; c < k; c++) nxt[c] = sb.fr() + (uint64_t)c * n_out;
+        for (int base = 0; base < k; base += GM_MAX_COLS) {
+            ColPtrs ci;
+            ColPtrsMut co;
+            const int cnt = (k - base < GM_MAX_COLS) ? k - base : GM_MAX_COLS;
+            for (int i = 0; i < cnt; i++) { ci.p[i] = cur[base + i]; co.p[i] = const_cast<Fr*>(nxt[base + i]); }
+            const dim3 grid(ceil_div(n_out, 256), cnt);
+            if (lg == 3) hipLaunchKernelGGL(k_dense_eval<3>, grid, dim3(256), 0, s, ci, co, n_out, ep);
+            else if (lg == 2) hipLaunchKernelGGL(k_dense_eval<2>, grid, dim3(256), 0, s, ci, co, n_out, ep);
+            else if (lg == 1) hipLaunchKernelGGL(k_dense_eval<1>, grid, dim3(256), 0, s, ci, co, n_out, ep);
+            else hipLaunchKernelGGL(k_dense_eval<0>, grid, dim3(256), 0, s, ci, co, n_out, ep);
+            GM_LAUNCH_CHECK();
+        }
+        cur = nxt;
+        rem -= lg;
+        if (rem == 0) {   // n_out == 1: the k results lie back to back
+            GM_HIP(hipMemcpyAsync(h_out, sb.p, (size_t)k * sizeof(Fr), hipMemcpyDeviceToHost, s));
+            GM_HIP(hipStreamSynchronize(s));
+            return GM_OK;
+        }
+    }
 }
 
 // levels[i] must hold 2^i elements (i = 0..nvars); level i = eq(pt[0..i], .) * mult   (pt[0] = MSB)
@@ -447,6 +513,19 @@ extern "C" int32_t gm_dense_bind(const uint64_t* const* d_in, uint64_t* const* d
     memcpy(&t, h_t, 32);
     return launch_dense_fold(reinterpret_cast<const Fr* const*>(d_in), reinterpret_cast<Fr* const*>(d_out), (int)k,
                              len / 2, t, as_stream(stream));
+}
+
+extern "C" int32_t gm_dense_evaluate(const uint64_t* const* d_cols, uint32_t k, uint32_t num_vars, const uint64_t* h_point, uint64_t* h_evs,
+                                     void* stream) {
+    GM_REQUIRE(d_cols && h_evs && (h_point || num_vars == 0), "null argument");
+    GM_REQUIRE(k >= 1 && num_vars <= 30, "bad shape: %u columns of 2^%u elements (1 column or more, num_vars <= 30)", k, num_vars);
+    for (uint32_t c = 0; c < k; c++) GM_REQUIRE(d_cols[c], "null column %u", c);
+    std::vector<Fr> pt(num_vars), ev(k);
+    if (num_vars) memcpy(pt.data(), h_point, 32 * (size_t)num_vars);
+    int32_t rc = launch_dense_evaluate(reinterpret_cast<const Fr* const*>(d_cols), (int)k, num_vars, pt.data(), ev.data(), as_stream(stream));
+    if (rc) return rc;
+    memcpy(h_evs, ev.data(), 32 * (size_t)k);
+    return GM_OK;
 }
 
 extern "C" int32_t gm_eq_table(const uint64_t* h_multiplier, const uint64_t* h_point, uint32_t nvars,

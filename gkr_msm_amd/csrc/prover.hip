@@ -43,6 +43,14 @@ int32_t gm_sc_bind(gm_sc* so, const uint64_t* h_t);
 int32_t gm_sc_final_evals(gm_sc* so, uint64_t* h_evals, uint32_t* n_evals);
 int32_t gm_sc_claim(const gm_sc* so, uint64_t* h_claim);
 int32_t gm_sc_destroy(gm_sc* so);
+int32_t gm_vv_map(const gm_fn* f, const gm_vv* in, gm_vv** out, void* stream);
+int32_t gm_vv_map_split(const gm_fn* f, const gm_vv* in, uint32_t bundle, gm_vv** out, void* stream);
+int32_t gm_vv_map_split_to_dense(const gm_fn* f, const gm_vv* in, uint32_t bundle, uint64_t* const* d_out, void* stream);
+int32_t gm_dense_map(const gm_fn* f, const uint64_t* const* d_in, uint64_t* const* d_out, uint64_t len, void* stream);
+int32_t gm_dense_map_split(const gm_fn* f, const uint64_t* const* d_in, uint64_t* const* d_out, uint64_t len, uint32_t split_lo_bit,
+                           uint32_t bundle, void* stream);
+int32_t gm_dense_evaluate(const uint64_t* const* d_cols, uint32_t k, uint32_t num_vars, const uint64_t* h_point, uint64_t* h_evs,
+                          void* stream);
 }
 
 namespace {
@@ -301,7 +309,10 @@ int32_t dense_deg2_prove(Tape* tr, const gm_fn& f, uint32_t num_vars, Claims* cl
                                     &h.so, s));
     if (LayerClock::on()) { LayerClock::get().create += LayerClock::now() - t0; LayerClock::get().layers++; }
     std::vector<Fr> pt, evs;
-    TRY(generic_sumcheck_prove(tr, h.so, num_vars, 3, &pt, &evs, (uint32_t)plan_of(f).n_ins));
+    int n_ins = 0, n_outs = 0, deg = 0;
+    if (fn_has_prog(&f)) TRY(fn_shape_any(f, &n_ins, &n_outs, &deg));   // a program never reaches a SegPlan
+    else n_ins = plan_of(f).n_ins;
+    TRY(generic_sumcheck_prove(tr, h.so, num_vars, 3, &pt, &evs, (uint32_t)n_ins));
     tr->write_scalars(evs);
     claims->point = pt;
     claims->evs = evs;
@@ -723,6 +734,8 @@ struct gm_gkr_witness {
     std::vector<Layer> layers;
     Advice output;                      // last_step of the circuit, dense columns
     uint32_t out_vars = 0, n_claims = 0;
+    uint32_t in_cols = 0, in_vars = 0;  // the input polynomials (a VecVec counts its row + column variables)
+    std::vector<std::unique_ptr<ProgRef>> progs;   // programs of a caller-defined circuit, held while the witness lives
     ~gm_gkr_witness() { if (pinned) (void)hipHostFree(pinned); }
 };
 
@@ -755,6 +768,8 @@ extern "C" int32_t gm_triangle_witness_create(const uint64_t* const* d_cols, uin
     const uint32_t num_layers = num_vars - split_hi;
     TRY(dense_map_adv(mkfn(GM_FN_PROJ_L3, (int)num_layers + 3), w->advices.back(), &w->output, s));
     w->layers = triangle_layers(num_vars, split_hi);
+    w->in_cols = 12;
+    w->in_vars = num_vars;
     w->out_vars = split_hi;
     w->n_claims = 3 * (num_layers + 3);
     TRY(gkr_witness_finish(w.get(), ((size_t)12 * 96 << num_vars) + ((size_t)48 << 20)));
@@ -795,6 +810,8 @@ extern "C" int32_t gm_bintree_witness_create(const gm_vv* inputs, uint32_t num_a
         w->output = last;
     }
     w->layers = bintree_layers(num_vars, num_adds, row_logsize, do_bitcheck != 0);
+    w->in_cols = inputs->k;
+    w->in_vars = inputs->row_logsize + inputs->col_logsize;
     w->n_claims = 3;
     const uint64_t T = inputs->total, nr = inputs->nrows;
     const size_t bytes = (size_t)6 * 32 * (T + 4 * nr + 64) + ((size_t)48 << 20) + ((size_t)6 * 96 << (num_vars > 0 ? num_vars - 1 : 0));
@@ -869,6 +886,244 @@ extern "C" int32_t gm_gkr_prove_tr(const gm_gkr_witness* w, const uint64_t* h_cl
     GM_REQUIRE(w && h_claim_evs && tr && tr->challenge && (h_claim_point || !w->out_vars), "null argument");
     return gkr_prove(w, h_claim_point, h_claim_evs, nullptr, 0, tr, nullptr, 0, nullptr, h_final_point, n_final_point, h_final_evs,
                      n_final_evs, n_challenges, rounds);
+}
+
+// =================================================================================================================
+// Caller-defined circuits: the builders above generalised to a gm_gkr_layer list (include/gkrmsm.h).  Maps go through the public
+// entry points (gm_dense_map*, gm_vv_map*), which send program functions to their own kernels and built-in ids to the built-in
+// ones -- the helpers above (dense_map_adv, adv_map*) build SegPlans and serve built-in ids only.
+namespace gm {
+
+// ZeroCheck on the device: one flag word per workgroup, non-zero when a word of the n-element columns a and b is (the host ORs them)
+__global__ void __launch_bounds__(256) k_zero_check(const Fr* __restrict__ a, const Fr* __restrict__ b, uint64_t n,
+                                                     uint32_t* __restrict__ flags) {
+    __shared__ uint32_t part[256];
+    uint32_t acc = 0;
+    for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256) {
+        const Fr x = fr_load(a + i), y = fr_load(b + i);
+#pragma unroll
+        for (int l = 0; l < 8; l++) acc |= x.l[l] | y.l[l];
+    }
+    part[threadIdx.x] = acc;
+    __syncthreads();
+    for (uint32_t h = 128; h > 0; h >>= 1) {
+        if (threadIdx.x < h) part[threadIdx.x] |= part[threadIdx.x + h];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) flags[blockIdx.x] = part[0];
+}
+
+}  // namespace gm
+
+namespace {
+
+uint32_t adv_cols(const Advice& a) { return a.kind == Advice::VECVEC ? a.vv->v->k : (uint32_t)a.cols.size(); }
+
+std::vector<uint64_t*> out_ptrs(const Advice& a) {
+    std::vector<uint64_t*> p;
+    for (auto& c : a.cols) p.push_back(reinterpret_cast<uint64_t*>(c->p));
+    return p;
+}
+
+int32_t circ_map(const gm_fn& f, int n_outs, const Advice& in, Advice* out, hipStream_t s) {
+    if (in.kind == Advice::DENSE) {
+        out->kind = Advice::DENSE;
+        out->len = in.len;
+        TRY(dense_alloc(n_outs, in.len, &out->cols));
+        return gm_dense_map(&f, in.col_ptrs().data(), out_ptrs(*out).data(), in.len, s);
+    }
+    gm_vv* o = nullptr;
+    TRY(gm_vv_map(&f, in.vv->v, &o, s));
+    out->kind = Advice::VECVEC;
+    out->vv.reset(new VVHolder(o));
+    return GM_OK;
+}
+
+// map + SplitAt in one launch: dense on index bit idx (LO) or num_vars - 1 - idx (HI); VecVec at LO(0), to dense once the rows have
+// one variable left (advice_map_split, bintree_add.rs:186-205: layer_idx + 2 == row_logsize)
+int32_t circ_map_split(const gm_fn& f, int n_outs, const Advice& in, uint32_t num_vars, bool hi, uint32_t idx, uint32_t bundle,
+                       Advice* out, hipStream_t s) {
+    if (in.kind == Advice::DENSE) {
+        out->kind = Advice::DENSE;
+        out->len = in.len / 2;
+        TRY(dense_alloc(2 * n_outs, out->len, &out->cols));
+        return gm_dense_map_split(&f, in.col_ptrs().data(), out_ptrs(*out).data(), in.len, hi ? num_vars - 1 - idx : idx, bundle, s);
+    }
+    const gm_vv* v = in.vv->v;
+    if (v->row_logsize == 1) {
+        out->kind = Advice::DENSE;
+        out->len = 1ull << v->col_logsize;
+        TRY(dense_alloc(2 * n_outs, out->len, &out->cols));
+        return gm_vv_map_split_to_dense(&f, v, bundle, out_ptrs(*out).data(), s);
+    }
+    gm_vv* o = nullptr;
+    TRY(gm_vv_map_split(&f, v, bundle, &o, s));
+    out->kind = Advice::VECVEC;
+    out->vv.reset(new VVHolder(o));
+    return GM_OK;
+}
+
+// ZeroCheck (zero_check.rs:17-33): the last two columns must vanish -- on VecVec advice their pads too, they are part of the
+// polynomial -- and are dropped
+int32_t circ_zero_check(const Advice& in, uint32_t layer, Advice* out, hipStream_t s) {
+    const uint32_t k = adv_cols(in);
+    const Fr *a, *b;
+    uint64_t n;
+    if (in.kind == Advice::VECVEC) {
+        const gm_vv* v = in.vv->v;
+        for (uint32_t c = k - 2; c < k; c++)
+            GM_REQUIRE(fr_is_zero(v->row_pad[c]) && fr_is_zero(v->col_pad[c]), "layer %u (ZEROCHECK): column %u has a non-zero pad", layer, c);
+        a = v->cols[k - 2]->fr(); b = v->cols[k - 1]->fr(); n = v->total;
+    } else {
+        a = in.cols[k - 2]->fr(); b = in.cols[k - 1]->fr(); n = in.len;
+    }
+    if (n) {
+        const unsigned blocks = (unsigned)std::min<uint64_t>(ceil_div(n, 256), 1024);
+        DevBuf flags;
+        TRY(flags.alloc(blocks * sizeof(uint32_t)));
+        hipLaunchKernelGGL(k_zero_check, dim3(blocks), dim3(256), 0, s, a, b, n, static_cast<uint32_t*>(flags.p));
+        GM_LAUNCH_CHECK();
+        std::vector<uint32_t> h(blocks);
+        GM_HIP(hipMemcpyAsync(h.data(), flags.p, blocks * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        GM_HIP(hipStreamSynchronize(s));
+        for (uint32_t x : h) GM_REQUIRE(x == 0, "layer %u (ZEROCHECK): columns %u and %u are not all zero", layer, k - 2, k - 1);
+    }
+    if (in.kind == Advice::VECVEC) {
+        gm_vv* o = nullptr;
+        TRY(gm_vv_slice(in.vv->v, 0, k - 2, &o));
+        out->kind = Advice::VECVEC;
+        out->vv.reset(new VVHolder(o));
+    } else {
+        out->kind = Advice::DENSE;
+        out->len = in.len;
+        out->cols.assign(in.cols.begin(), in.cols.end() - 2);
+    }
+    return GM_OK;
+}
+
+// workspace of one layer's sumcheck object over k columns, as the two built-in builders size it
+size_t circ_layer_arena(const Advice& a, uint32_t k, uint32_t num_vars) {
+    if (a.kind == Advice::VECVEC)
+        return (size_t)(k + 1) * 32 * (a.vv->v->total + 4 * (uint64_t)a.vv->v->nrows + 64) + ((size_t)(k + 1) * 96 << num_vars);
+    return (size_t)(k + 1) * 96 << num_vars;
+}
+
+int32_t circuit_witness_create(const gm_gkr_layer* layers, uint32_t n_layers, Advice in, uint32_t in_vars, int vv_row_logsize,
+                               gm_gkr_witness** out, hipStream_t s) {
+    CircuitShape S;
+    TRY(circuit_shape(layers, n_layers, adv_cols(in), in_vars, vv_row_logsize, &S));   // before any device work
+    std::unique_ptr<gm_gkr_witness> w(new gm_gkr_witness());
+    w->stream = s;
+    for (const Layer& L : S.layers)
+        if (L.kind == Layer::DENSE && fn_has_prog(&L.f)) {
+            ProgFn pf;
+            TRY(prog_fn_parse(&L.f, &pf));
+            w->progs.emplace_back(new ProgRef(pf));
+        }
+    size_t arena = 0;
+    Advice cur = in;
+    for (size_t i = 0; i < S.layers.size(); i++) {
+        Layer& L = S.layers[i];
+        Advice next;
+        if (L.kind == Layer::DENSE) {   // MAP: the layer kind follows its advice
+            L.kind = cur.kind == Advice::VECVEC ? Layer::VECVEC : Layer::DENSE;
+            arena = std::max(arena, circ_layer_arena(cur, adv_cols(cur), L.num_vars));
+            int ni = 0, no = 0, dg = 0;
+            TRY(fn_shape_any(L.f, &ni, &no, &dg));
+            w->advices.push_back(cur);
+            if (i + 1 < S.layers.size() && S.layers[i + 1].kind == Layer::SPLIT) {   // fused map-split
+                const Layer& P = S.layers[i + 1];
+                TRY(circ_map_split(L.f, no, cur, L.num_vars, P.split_hi, P.split_idx, P.bundle, &next, s));
+                w->advices.push_back(Advice());
+                i++;
+            } else {
+                TRY(circ_map(L.f, no, cur, &next, s));
+            }
+        } else if (L.kind == Layer::SPLIT) {   // no map in front: an identity map-split (GlueSplit::witness, splits.rs:172-176)
+            const uint32_t k = adv_cols(cur);
+            TRY(circ_map_split(mkfn(GM_FN_ID, (int)k), (int)k, cur, L.num_vars, L.split_hi, L.split_idx, L.bundle, &next, s));
+            w->advices.push_back(Advice());
+        } else {
+            TRY(circ_zero_check(cur, (uint32_t)i, &next, s));
+            w->advices.push_back(Advice());
+        }
+        cur = next;
+    }
+    w->out_vars = S.out_vars;
+    if (cur.kind == Advice::VECVEC) {   // densify the output
+        w->output.kind = Advice::DENSE;
+        w->output.len = 1ull << S.out_vars;
+        TRY(dense_alloc(adv_cols(cur), w->output.len, &w->output.cols));
+        TRY(gm_vv_to_dense(cur.vv->v, out_ptrs(w->output).data(), s));
+    } else {
+        w->output = cur;
+    }
+    GM_REQUIRE(w->output.len == (1ull << S.out_vars) && w->output.cols.size() == S.out_cols, "circuit output has an unexpected shape");
+    w->layers = S.layers;
+    w->in_cols = S.in_cols;
+    w->in_vars = S.in_vars;
+    w->n_claims = S.out_cols;
+    TRY(gkr_witness_finish(w.get(), arena + ((size_t)48 << 20)));
+    *out = w.release();
+    return GM_OK;
+}
+
+}  // namespace
+
+extern "C" int32_t gm_gkr_circuit_witness_create(const gm_gkr_layer* layers, uint32_t n_layers, const uint64_t* const* d_cols,
+                                                 uint32_t n_cols, uint32_t num_vars, gm_gkr_witness** out, void* stream) {
+    GM_REQUIRE(layers && d_cols && out, "null argument");
+    GM_REQUIRE(n_cols >= 1 && n_cols <= GM_MAX_COLS && num_vars <= 40, "%u input columns of 2^%u elements", n_cols, num_vars);
+    Advice in;
+    in.kind = Advice::DENSE;
+    in.len = (uint64_t)1 << num_vars;
+    for (uint32_t i = 0; i < n_cols; i++) {
+        GM_REQUIRE(d_cols[i], "null input column %u", i);
+        in.cols.emplace_back(new DevBuf());
+        in.cols.back()->p = const_cast<uint64_t*>(d_cols[i]);  // borrowed: the caller keeps the inputs alive
+        in.cols.back()->owned = false;
+        in.cols.back()->bytes = (size_t)in.len * sizeof(Fr);
+    }
+    return circuit_witness_create(layers, n_layers, in, num_vars, -1, out, as_stream(stream));
+}
+
+extern "C" int32_t gm_gkr_circuit_witness_create_vv(const gm_gkr_layer* layers, uint32_t n_layers, const gm_vv* inputs,
+                                                    gm_gkr_witness** out, void* stream) {
+    GM_REQUIRE(layers && inputs && out, "null argument");
+    GM_REQUIRE(!inputs->sharded, "standalone circuit over a sharded polynomial");
+    gm_vv* share = nullptr;
+    TRY(gm_vv_slice(inputs, 0, inputs->k, &share));  // shares the caller's columns
+    Advice in;
+    in.kind = Advice::VECVEC;
+    in.vv.reset(new VVHolder(share));
+    return circuit_witness_create(layers, n_layers, in, inputs->row_logsize + inputs->col_logsize, (int)inputs->row_logsize, out,
+                                  as_stream(stream));
+}
+
+// "claim computation" (pippenger.rs:531-541) on the device: evaluate_poly(output column, point) for every output column
+extern "C" int32_t gm_gkr_witness_claims(const gm_gkr_witness* w, const uint64_t* h_point, uint64_t* h_evs, uint32_t* n_evs) {
+    GM_REQUIRE(w && h_evs && (h_point || !w->out_vars), "null argument");
+    std::vector<const uint64_t*> cols;
+    for (auto& c : w->output.cols) cols.push_back(reinterpret_cast<const uint64_t*>(c->p));
+    const Fr zero = fr_zero();
+    TRY(gm_dense_evaluate(cols.data(), (uint32_t)cols.size(), w->out_vars, h_point ? h_point : reinterpret_cast<const uint64_t*>(&zero),
+                          h_evs, w->stream));
+    if (n_evs) *n_evs = (uint32_t)cols.size();
+    return GM_OK;
+}
+
+// the layer list of any gm_gkr_witness, for gm_gkr_verify(_tr)
+extern "C" int32_t gm_gkr_witness_layers(const gm_gkr_witness* w, gm_gkr_layer* h_layers, uint32_t layers_cap, uint32_t* n_layers,
+                                         uint32_t* input_cols, uint32_t* input_num_vars) {
+    GM_REQUIRE(w, "null witness");
+    if (n_layers) *n_layers = (uint32_t)w->layers.size();
+    if (input_cols) *input_cols = w->in_cols;
+    if (input_num_vars) *input_num_vars = w->in_vars;
+    if (h_layers) {
+        GM_REQUIRE(layers_cap >= w->layers.size(), "layer array too small (%u < %zu)", layers_cap, w->layers.size());
+        for (size_t i = 0; i < w->layers.size(); i++) h_layers[i] = layer_public(w->layers[i]);
+    }
+    return GM_OK;
 }
 
 // =================================================================================================================

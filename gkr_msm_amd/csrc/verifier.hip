@@ -126,8 +126,13 @@ int32_t sumcheck_verify(Reader* tr, uint32_t degree, uint32_t num_vars, Fr* clai
 
 // DenseDeg2Sumcheck::verify (dense_eq.rs:223-237) = VecVecDeg2Sumcheck::verify (vecvec_eq.rs:452-467) = DenseEqSumcheck::verify
 // (sumcheck.rs:874-889): the three differ only in the prover object
+// A program function (gm_fn_program_create) is evaluated by the program host evaluator: it never reaches a SegPlan.
 int32_t layer_verify(Reader* tr, const gm_fn& f, uint32_t num_vars, VClaims* c, const char* what) {
-    const SegPlan sp = plan_of(f);
+    ProgFn pf;
+    TRY(prog_fn_parse(&f, &pf));
+    SegPlan sp;
+    if (pf.nseg) { sp.n_ins = pf.n_ins; sp.n_outs = pf.n_outs; }
+    else sp = plan_of(f);
     Fr gamma;
     TRY(tr->challenge(&gamma));
     VERIFY((int)c->evs.size() == sp.n_outs, "%s: %zu claims for a function with %d outputs", what, c->evs.size(), sp.n_outs);
@@ -136,7 +141,8 @@ int32_t layer_verify(Reader* tr, const gm_fn& f, uint32_t num_vars, VClaims* c, 
     TRY(sumcheck_verify(tr, 3, num_vars, &ev, &out_pt));   // degrees = f.deg() + 1 with f.deg() = 2 for every layer function
     std::vector<Fr> poly_evs(sp.n_ins), fo(sp.n_outs);
     TRY(tr->read_scalars(sp.n_ins, poly_evs.data()));
-    seg_plan_exec_host(sp, poly_evs.data(), fo.data());
+    if (pf.nseg) prog_fn_exec_host(pf, poly_evs.data(), fo.data());
+    else seg_plan_exec_host(sp, poly_evs.data(), fo.data());
     VERIFY(c->point.size() == out_pt.size(), "%s: claim point has %zu coordinates, the layer %u variables", what, c->point.size(), num_vars);
     VERIFY(fr_eq(fr_mul(gamma_rlc(gamma, fo), eq_eval(c->point, out_pt)), ev), "Final combinator check has failed (%s, %u variables)",
            what, num_vars);
@@ -656,5 +662,70 @@ extern "C" int32_t gm_gkr_msm_verify_tr(uint32_t log_num_points, uint32_t log_nu
                               reinterpret_cast<Fr*>(h_final_evs), rounds);
     } catch (const std::exception& e) {
         return set_err(GM_ERR_INVALID, "gm_gkr_msm_verify_tr: %s", e.what());
+    }
+}
+
+// =================================================================================================================
+// Caller-defined circuits: SimpleGKR::verify (gkr.rs:52-58) over a gm_gkr_layer list, with the per-layer numbers of variables the
+// shape pass derives from the input (the same pass gm_gkr_circuit_witness_create runs).
+namespace {
+
+int32_t circuit_verify(Reader* rd, const gm_gkr_layer* layers, uint32_t n_layers, uint32_t input_cols, uint32_t input_num_vars,
+                       const uint64_t* h_claim_point, const uint64_t* h_claim_evs, uint64_t* h_final_point, uint32_t* n_final_point,
+                       uint64_t* h_final_evs, uint32_t* n_final_evs) {
+    CircuitShape S;
+    TRY(circuit_shape(layers, n_layers, input_cols, input_num_vars, -1, &S));
+    GM_REQUIRE(h_claim_evs && (h_claim_point || !S.out_vars), "null argument");
+    VClaims c;
+    c.point.resize(S.out_vars);
+    if (S.out_vars) memcpy(c.point.data(), h_claim_point, 32 * (size_t)S.out_vars);
+    c.evs.resize(S.out_cols);
+    memcpy(c.evs.data(), h_claim_evs, 32 * (size_t)S.out_cols);
+    TRY(gkr_verify(rd, S.layers, &c, "caller circuit"));
+    // the shape pass fixes both sizes; a well-formed proof cannot miss them
+    VERIFY(c.point.size() == S.in_vars && c.evs.size() == S.in_cols, "final claims have %zu coordinates / %zu evaluations, expected %u / %u",
+           c.point.size(), c.evs.size(), S.in_vars, S.in_cols);
+    if (n_final_point) *n_final_point = (uint32_t)c.point.size();
+    if (h_final_point) memcpy(h_final_point, c.point.data(), c.point.size() * sizeof(Fr));
+    if (n_final_evs) *n_final_evs = (uint32_t)c.evs.size();
+    if (h_final_evs) memcpy(h_final_evs, c.evs.data(), c.evs.size() * sizeof(Fr));
+    return GM_OK;
+}
+
+}  // namespace
+
+extern "C" int32_t gm_gkr_verify(const gm_gkr_layer* layers, uint32_t n_layers, uint32_t input_cols, uint32_t input_num_vars,
+                                 const uint64_t* h_claim_point, const uint64_t* h_claim_evs, const uint64_t* h_msgs, uint64_t n_msgs,
+                                 const uint64_t* h_tape, uint64_t n_tape, uint64_t* h_final_point, uint32_t* n_final_point,
+                                 uint64_t* h_final_evs, uint32_t* n_final_evs, uint64_t* tape_used) {
+    try {
+        GM_REQUIRE((h_msgs || !n_msgs) && (h_tape || !n_tape), "null argument");
+        Reader rd;
+        rd.scalars = reinterpret_cast<const Fr*>(h_msgs);
+        rd.tape = h_tape;
+        rd.n_scalars = n_msgs; rd.n_tape = n_tape;
+        TRY(circuit_verify(&rd, layers, n_layers, input_cols, input_num_vars, h_claim_point, h_claim_evs, h_final_point, n_final_point,
+                           h_final_evs, n_final_evs));
+        if (rd.si != n_msgs)
+            return set_err(GM_ERR_VERIFY, "proof has unread messages (%llu of %llu scalars read)", (unsigned long long)rd.si,
+                           (unsigned long long)n_msgs);
+        if (tape_used) *tape_used = rd.pos;
+        return GM_OK;
+    } catch (const std::exception& e) {
+        return set_err(GM_ERR_INVALID, "gm_gkr_verify: %s", e.what());
+    }
+}
+
+extern "C" int32_t gm_gkr_verify_tr(const gm_gkr_layer* layers, uint32_t n_layers, uint32_t input_cols, uint32_t input_num_vars,
+                                    const uint64_t* h_claim_point, const uint64_t* h_claim_evs, const gm_transcript_reader* tr,
+                                    uint64_t* h_final_point, uint32_t* n_final_point, uint64_t* h_final_evs, uint32_t* n_final_evs) {
+    try {
+        GM_REQUIRE(tr && tr->read_scalars && tr->challenge, "null argument");
+        Reader rd;
+        rd.cb = tr;
+        return circuit_verify(&rd, layers, n_layers, input_cols, input_num_vars, h_claim_point, h_claim_evs, h_final_point, n_final_point,
+                              h_final_evs, n_final_evs);
+    } catch (const std::exception& e) {
+        return set_err(GM_ERR_INVALID, "gm_gkr_verify_tr: %s", e.what());
     }
 }

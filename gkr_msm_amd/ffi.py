@@ -44,6 +44,18 @@ class GmFnTerm(C.Structure):
 assert C.sizeof(GmFnTerm) == 40
 
 
+GKR_MAP, GKR_SPLIT, GKR_ZEROCHECK = 0, 1, 2
+
+
+class GmGkrLayer(C.Structure):
+    """gm_gkr_layer: one layer of a caller-defined GKR circuit (MAP f / SPLIT at HI or LO(split_idx) with bundle / ZEROCHECK)"""
+    _fields_ = [("kind", C.c_int32), ("f", GmFn), ("split_hi", C.c_uint32), ("split_idx", C.c_uint32), ("bundle", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+assert C.sizeof(GmGkrLayer) == 56
+
+
 _lib = None
 
 u64p = C.POINTER(C.c_uint64)
@@ -264,6 +276,15 @@ _SIGS = {
     "gm_gkr_witness_output": (C.c_int32, [vp, vp, C.c_uint32, u32p, u32p]),
     "gm_gkr_prove": (C.c_int32, [vp, vp, vp, vp, C.c_uint64, vp, C.c_uint64, u64p, vp, u32p, vp, u32p, u64p, u64p]),
     "gm_gkr_prove_tr": (C.c_int32, [vp, vp, vp, C.POINTER(GmTranscript), vp, u32p, vp, u32p, u64p, u64p]),
+    "gm_gkr_circuit_witness_create": (C.c_int32, [C.POINTER(GmGkrLayer), C.c_uint32, vp, C.c_uint32, C.c_uint32, C.POINTER(vp), vp]),
+    "gm_gkr_circuit_witness_create_vv": (C.c_int32, [C.POINTER(GmGkrLayer), C.c_uint32, vp, C.POINTER(vp), vp]),
+    "gm_gkr_witness_claims": (C.c_int32, [vp, vp, vp, u32p]),
+    "gm_gkr_witness_layers": (C.c_int32, [vp, C.POINTER(GmGkrLayer), C.c_uint32, u32p, u32p, u32p]),
+    "gm_gkr_verify": (C.c_int32, [C.POINTER(GmGkrLayer), C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, C.c_uint64, vp, C.c_uint64,
+                                  vp, u32p, vp, u32p, u64p]),
+    "gm_gkr_verify_tr": (C.c_int32, [C.POINTER(GmGkrLayer), C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, C.POINTER(GmTranscriptReader),
+                                     vp, u32p, vp, u32p]),
+    "gm_dense_evaluate": (C.c_int32, [vp, C.c_uint32, C.c_uint32, vp, vp, vp]),
     "gm_g1_release_scratch": (C.c_int32, []),
     "gm_g1_generator": (C.c_int32, [vp]),
     "gm_g1_fixed_base_register": (C.c_int32, [vp, C.c_uint64, vp]),

@@ -1016,6 +1016,129 @@ class GkrWitness:
                     evs=codec.from_mont_limbs(fev[: nev.value]), tape_used=used.value, rounds=rounds.value)
 
 
+def gkr_layers(spec):
+    """[("map", GmFn) | ("split", hi, idx, bundle) | ("zerocheck",), ...] -> a ctypes array of gm_gkr_layer"""
+    arr = (ffi.GmGkrLayer * max(len(spec), 1))()
+    for i, l in enumerate(spec):
+        if l[0] == "map":
+            arr[i].kind, arr[i].f = ffi.GKR_MAP, l[1]
+        elif l[0] == "split":
+            arr[i].kind, arr[i].split_hi, arr[i].split_idx, arr[i].bundle = ffi.GKR_SPLIT, 1 if l[1] else 0, l[2], l[3]
+        elif l[0] == "zerocheck":
+            arr[i].kind = ffi.GKR_ZEROCHECK
+        else:
+            raise ValueError(l[0])
+    return arr
+
+
+def gkr_layers_spec(arr, n):
+    """the inverse of gkr_layers"""
+    out = []
+    for l in arr[:n]:
+        if l.kind == ffi.GKR_MAP:
+            f = ffi.GmFn()
+            C.memmove(C.byref(f), C.byref(l.f), C.sizeof(ffi.GmFn))
+            out.append(("map", f))
+        elif l.kind == ffi.GKR_SPLIT:
+            out.append(("split", bool(l.split_hi), l.split_idx, l.bundle))
+        else:
+            out.append(("zerocheck",))
+    return out
+
+
+class GkrCircuit(GkrWitness):
+    """a caller-defined GKR circuit (gm_gkr_circuit_witness_create*): a gm_gkr_witness over the layer list `spec` (see gkr_layers)"""
+
+    @staticmethod
+    def dense(spec, cols, num_vars):
+        h = C.c_void_p()
+        ffi.check(ffi.lib().gm_gkr_circuit_witness_create(gkr_layers(spec), len(spec), ptr_array(cols), len(cols), num_vars, C.byref(h),
+                                                          cur_stream()))
+        return GkrCircuit(h, tuple(cols))
+
+    @staticmethod
+    def vecvec(spec, vv):
+        h = C.c_void_p()
+        ffi.check(ffi.lib().gm_gkr_circuit_witness_create_vv(gkr_layers(spec), len(spec), vv.h, C.byref(h), cur_stream()))
+        return GkrCircuit(h, (vv,))
+
+
+def gkr_witness_claims(w, point):
+    """gm_gkr_witness_claims: the output columns of any gm_gkr_witness evaluated at point (canonical ints)"""
+    n = C.c_uint32()
+    ffi.check(w.L.gm_gkr_witness_output(w.h, None, 0, C.byref(n), None))
+    evs = np.zeros((max(n.value, 1), 4), dtype=np.uint64)
+    p = fr_arg(point if point else [0])
+    ffi.check(w.L.gm_gkr_witness_claims(w.h, p.ctypes.data, evs.ctypes.data, C.byref(n)))
+    return codec.from_mont_limbs(evs[: n.value])
+
+
+def gkr_witness_layers(w):
+    """gm_gkr_witness_layers -> (layer spec, input column count, input num_vars)"""
+    n, ic, iv = C.c_uint32(), C.c_uint32(), C.c_uint32()
+    ffi.check(w.L.gm_gkr_witness_layers(w.h, None, 0, C.byref(n), C.byref(ic), C.byref(iv)))
+    arr = (ffi.GmGkrLayer * max(n.value, 1))()
+    ffi.check(w.L.gm_gkr_witness_layers(w.h, arr, n.value, C.byref(n), C.byref(ic), C.byref(iv)))
+    return gkr_layers_spec(arr, n.value), ic.value, iv.value
+
+
+def dense_evaluate(cols, num_vars, point):
+    """gm_dense_evaluate of device columns (torch tensors) at point -> canonical ints"""
+    evs = np.zeros((len(cols), 4), dtype=np.uint64)
+    p = fr_arg(point if point else [0])
+    ffi.check(ffi.lib().gm_dense_evaluate(ptr_array(cols), len(cols), num_vars, p.ctypes.data, evs.ctypes.data, cur_stream()))
+    return codec.from_mont_limbs(evs)
+
+
+def gkr_verify(spec, input_cols, input_num_vars, claim_point, claim_evs, msgs, tape):
+    """gm_gkr_verify over recorded messages and a challenge tape -> (rc, dict(point, evs, tape_used)); rc != 0 is returned, not raised"""
+    L = ffi.lib()
+    cp, ce = fr_arg(claim_point if claim_point else [0]), fr_arg(claim_evs)
+    m = fr_arg(msgs if msgs else [0])
+    tp = codec.ints_to_limbs(tape if tape else [0])
+    fpt, fev = np.zeros((64, 4), dtype=np.uint64), np.zeros((64, 4), dtype=np.uint64)
+    npt, nev, used = C.c_uint32(), C.c_uint32(), C.c_uint64()
+    rc = L.gm_gkr_verify(gkr_layers(spec), len(spec), input_cols, input_num_vars, cp.ctypes.data, ce.ctypes.data, m.ctypes.data, len(msgs),
+                         tp.ctypes.data, len(tape), fpt.ctypes.data, C.byref(npt), fev.ctypes.data, C.byref(nev), C.byref(used))
+    if rc:
+        return rc, None
+    return rc, dict(point=codec.from_mont_limbs(fpt[: npt.value]), evs=codec.from_mont_limbs(fev[: nev.value]), tape_used=used.value)
+
+
+def gkr_prove_tr(w, claim_point, claim_evs, transcript):
+    """gm_gkr_prove_tr under a live transcript (MerlinTranscript / LiveTranscript) -> dict(point, evs, n_challenges, rounds)"""
+    cp, ce = fr_arg(claim_point if claim_point else [0]), fr_arg(claim_evs)
+    fpt, fev = np.zeros((64, 4), dtype=np.uint64), np.zeros((64, 4), dtype=np.uint64)
+    npt, nev, used, rounds = C.c_uint32(), C.c_uint32(), C.c_uint64(), C.c_uint64()
+    ffi.check(w.L.gm_gkr_prove_tr(w.h, cp.ctypes.data, ce.ctypes.data, C.byref(transcript.c), fpt.ctypes.data, C.byref(npt),
+                                  fev.ctypes.data, C.byref(nev), C.byref(used), C.byref(rounds)))
+    return dict(point=codec.from_mont_limbs(fpt[: npt.value]), evs=codec.from_mont_limbs(fev[: nev.value]), n_challenges=used.value,
+                rounds=rounds.value)
+
+
+def gkr_verify_merlin(spec, input_cols, input_num_vars, claim_point, claim_evs, proof, label=b"gkr-msm"):
+    """gm_gkr_verify_tr over gm_merlin_create_verifier(proof) -> (rc, dict(point, evs, unread))"""
+    L = ffi.lib()
+    h = C.c_void_p()
+    pb = C.create_string_buffer(bytes(proof), max(len(proof), 1))
+    ffi.check(L.gm_merlin_create_verifier(label, len(label), pb, len(proof), C.byref(h)))
+    try:
+        rd = ffi.GmTranscriptReader()
+        ffi.check(L.gm_merlin_reader(h, C.byref(rd)))
+        cp, ce = fr_arg(claim_point if claim_point else [0]), fr_arg(claim_evs)
+        fpt, fev = np.zeros((64, 4), dtype=np.uint64), np.zeros((64, 4), dtype=np.uint64)
+        npt, nev = C.c_uint32(), C.c_uint32()
+        rc = L.gm_gkr_verify_tr(gkr_layers(spec), len(spec), input_cols, input_num_vars, cp.ctypes.data, ce.ctypes.data, C.byref(rd),
+                                fpt.ctypes.data, C.byref(npt), fev.ctypes.data, C.byref(nev))
+        left = C.c_uint64()
+        ffi.check(L.gm_merlin_unread(h, C.byref(left)))
+        if rc:
+            return rc, None
+        return rc, dict(point=codec.from_mont_limbs(fpt[: npt.value]), evs=codec.from_mont_limbs(fev[: nev.value]), unread=left.value)
+    finally:
+        L.gm_merlin_destroy(h)
+
+
 def sc_profile(mode):
     ffi.check(ffi.lib().gm_sc_profile(mode))
 

@@ -116,9 +116,10 @@ int32_t gm_fn_shape(const gm_fn* f, int32_t* n_ins, int32_t* n_outs, int32_t* de
  * n_terms <= GM_FN_PROG_MAX_TERMS, factor indices < n_ins, out < n_outs, reserved == 0.
  * Program functions run on the device in gm_dense_map, gm_dense_map_split, gm_vv_map, gm_vv_map_split,
  * gm_vv_map_split_to_dense, gm_sc_dense_deg2_create / gm_sc_vecvec_deg2_create (deg 2) and gm_sc_dense_create kind 0
- * (deg 1 .. 3); on the host in gm_fn_host.  The whole-protocol drivers keep their built-in layers.
- * Lifetime: each device receives its own copy of the term table on first use.  A sumcheck object holds a reference:
- * gm_fn_program_destroy returns GM_ERR_STATE while one exists.  Otherwise it synchronises every device holding a copy
+ * (deg 1 .. 3); on the host in gm_fn_host; as layer functions of caller-defined circuits (gm_gkr_circuit_witness_create*,
+ * gm_gkr_verify(_tr), below).  The Pippenger, pushforward and gen-1 drivers keep their built-in layers.
+ * Lifetime: each device receives its own copy of the term table on first use.  A sumcheck object or a circuit witness holds a
+ * reference: gm_fn_program_destroy returns GM_ERR_STATE while one exists.  Otherwise it synchronises every device holding a copy
  * (maps are asynchronous) and frees them; call it from a thread that has no sumcheck round waiting for a challenge.
  * An unknown or destroyed id is GM_ERR_INVALID everywhere; ids are not reused within a process. */
 #define GM_FN_PROG_BASE 4096   /* program ids are >= this; built-in ids stay < 64 */
@@ -163,6 +164,11 @@ int32_t gm_dense_bind(const uint64_t* const* d_in, uint64_t* const* d_out, uint3
                       const uint64_t* h_t, void* stream);
 int32_t gm_eq_table(const uint64_t* h_multiplier, const uint64_t* h_point, uint32_t nvars, uint64_t* d_scratch,
                     uint64_t* d_out, void* stream);
+/* gm_dense_evaluate  evaluate_poly (cleanup/utils/arith.rs:6-9) of k device columns of 2^num_vars elements (num_vars <= 30) at one
+ *                    point: point[0] is the most significant variable, the lowest index bit pairs with point[num_vars - 1] -- the
+ *                    value gm_dense_bind repeated num_vars times leaves, bit for bit.  h_evs: k elements; returns when they are there. */
+int32_t gm_dense_evaluate(const uint64_t* const* d_cols, uint32_t k, uint32_t num_vars, const uint64_t* h_point, uint64_t* h_evs,
+                          void* stream);
 
 /* ---------------------------------------------------------------- VecVec polynomials (a2, a3, a12)
  * gm_vv = k `VecVecPolynomial`s sharing one row structure (cleanup/polys/vecvec.rs:149-160): rows stored back to
@@ -559,6 +565,62 @@ int32_t gm_gkr_prove(const gm_gkr_witness* w, const uint64_t* h_claim_point, con
 int32_t gm_gkr_prove_tr(const gm_gkr_witness* w, const uint64_t* h_claim_point, const uint64_t* h_claim_evs,
                         const gm_transcript* tr, uint64_t* h_final_point, uint32_t* n_final_point, uint64_t* h_final_evs,
                         uint32_t* n_final_evs, uint64_t* n_challenges, uint64_t* rounds);
+
+/* ---------------------------------------------------------------- caller-defined GKR circuits
+ * SimpleGKR::new(layers) (gkrs/gkr.rs:14-58) over the caller's own layers, listed from input to output; the prover and the
+ * verifier run the list in reverse.  One gm_gkr_layer per layer:
+ *   GM_GKR_MAP        f over the current columns (dense, or VecVec while the input still is): f.n_ins == current column count,
+ *                     deg(f) == 2 (dense_eq.rs:200, vecvec_eq.rs:426); the column count becomes f.n_outs.  Built-in ids or
+ *                     program ids, not both in one gm_fn.
+ *   GM_GKR_SPLIT      SplitAt(HI(split_idx) if split_hi else LO(split_idx), bundle) (splits.rs:112-147): bundle divides the column
+ *                     count, split_idx < the current number of variables (>= 1); the columns double, one variable goes.
+ *                     On VecVec columns only LO(0).
+ *   GM_GKR_ZEROCHECK  ZeroCheck (zero_check.rs:17-33): the last two current columns are all zero and are dropped (>= 2 columns).
+ * reserved == 0; f is read for MAP layers only.  At most GM_MAX_COLS (64) columns anywhere.  Every rule is checked in one host
+ * pass before any device work; a violation is GM_ERR_INVALID naming the layer.
+ *   gm_gkr_circuit_witness_create     dense input: n_cols device columns of 2^num_vars elements (borrowed, not copied)
+ *   gm_gkr_circuit_witness_create_vv  VecVec input (shared with the caller, like gm_bintree_witness_create's)
+ *     The builder of bintree_add.rs:137-239 / triangle_add.rs:101-158 generalised: a layer's advice is its input (EMPTY for SPLIT
+ *     and ZEROCHECK); a MAP followed by a SPLIT is one fused map-split (VecVec with row_logsize 1 goes to dense there, the
+ *     `layer_idx + 2 == row_logsize` rule of advice_map_split); a SPLIT with no MAP in front is an identity map-split (GlueSplit).
+ *     ZEROCHECK checks on the device that its two columns are zero (VecVec: and that their row / column pads are) and refuses the
+ *     witness otherwise (GM_ERR_INVALID).  The result is a gm_gkr_witness: gm_gkr_witness_output (a VecVec output is densified),
+ *     gm_gkr_prove(_tr) and gm_gkr_witness_destroy work on it unchanged.  The witness holds every program its layers use:
+ *     gm_fn_program_destroy returns GM_ERR_STATE until it is destroyed.
+ *   gm_gkr_witness_claims    evaluate_poly(output column, point) for every output column (pippenger.rs:531-541) with
+ *                            gm_dense_evaluate; h_evs: one element per output column; returns when they are on the host
+ *   gm_gkr_witness_layers    the layer list, the input column count and the input's number of variables of ANY gm_gkr_witness
+ *                            (the two built-in circuits included); h_layers may be NULL to query n_layers
+ *   gm_gkr_verify(_tr)       SimpleGKR::verify (gkr.rs:52-58) on the host: claims on the output (point of the output's variables,
+ *                            one evaluation per output column) -> claims on the input columns (point of input_num_vars elements,
+ *                            input_cols evaluations; for VecVec input, about its dense form).  GM_ERR_VERIFY: a check failed.
+ *                            The recorded form reads h_msgs (the prover's messages) and a challenge tape and insists that every
+ *                            message was read. */
+#define GM_GKR_MAP 0
+#define GM_GKR_SPLIT 1
+#define GM_GKR_ZEROCHECK 2
+typedef struct gm_gkr_layer {
+    int32_t kind;        /* GM_GKR_MAP / GM_GKR_SPLIT / GM_GKR_ZEROCHECK */
+    gm_fn f;             /* MAP: the layer function */
+    uint32_t split_hi;   /* SPLIT: 1 = HI(split_idx), 0 = LO(split_idx) */
+    uint32_t split_idx;
+    uint32_t bundle;
+    uint32_t reserved;   /* must be 0 */
+} gm_gkr_layer;          /* 56 bytes */
+int32_t gm_gkr_circuit_witness_create(const gm_gkr_layer* layers, uint32_t n_layers, const uint64_t* const* d_cols, uint32_t n_cols,
+                                      uint32_t num_vars, gm_gkr_witness** out, void* stream);
+int32_t gm_gkr_circuit_witness_create_vv(const gm_gkr_layer* layers, uint32_t n_layers, const gm_vv* inputs, gm_gkr_witness** out,
+                                         void* stream);
+int32_t gm_gkr_witness_claims(const gm_gkr_witness* w, const uint64_t* h_point, uint64_t* h_evs, uint32_t* n_evs);
+int32_t gm_gkr_witness_layers(const gm_gkr_witness* w, gm_gkr_layer* h_layers, uint32_t layers_cap, uint32_t* n_layers,
+                              uint32_t* input_cols, uint32_t* input_num_vars);
+int32_t gm_gkr_verify(const gm_gkr_layer* layers, uint32_t n_layers, uint32_t input_cols, uint32_t input_num_vars,
+                      const uint64_t* h_claim_point, const uint64_t* h_claim_evs, const uint64_t* h_msgs, uint64_t n_msgs,
+                      const uint64_t* h_tape, uint64_t n_tape, uint64_t* h_final_point, uint32_t* n_final_point,
+                      uint64_t* h_final_evs, uint32_t* n_final_evs, uint64_t* tape_used);
+int32_t gm_gkr_verify_tr(const gm_gkr_layer* layers, uint32_t n_layers, uint32_t input_cols, uint32_t input_num_vars,
+                         const uint64_t* h_claim_point, const uint64_t* h_claim_evs, const gm_transcript_reader* tr,
+                         uint64_t* h_final_point, uint32_t* n_final_point, uint64_t* h_final_evs, uint32_t* n_final_evs);
 
 /* ---------------------------------------------------------------- "prove pushforward" (a7, a10, a12, a13)
  * PushforwardProtocol::prove (pushforward/pushforward.rs:640-846) with LogupMainphaseProtocol (pushforward/logup_mainphase.rs:83-208)
