@@ -22,6 +22,7 @@
 
 #include "internal.hpp"
 #include "gkr_layers.hpp"
+#include "logup.hpp"
 #include "msm_plan.hpp"
 #include "vecvec.hpp"
 
@@ -1173,16 +1174,82 @@ int32_t gm_sc_dense_create(int32_t kind, const gm_fn* f, uint32_t num_vars, cons
 
 namespace {
 
-struct Frac {  // one (numerator, denominator) pair of the logup tree; the arrays may be halves of a parent's buffers
-    const Fr* num = nullptr;
-    const Fr* den = nullptr;
-    uint64_t len = 0;
-    std::shared_ptr<DevBuf> keep_n, keep_d;
-};
-
 int32_t read_fr(const Fr* d, Fr* h, hipStream_t s) {
     GM_HIP(hipMemcpyAsync(h, d, sizeof(Fr), hipMemcpyDeviceToHost, s));
     GM_HIP(hipStreamSynchronize(s));
+    return GM_OK;
+}
+
+// workspace of the sumcheck objects of a logup main phase whose widest layer has 2^top_log elements per column: fold buffers of the
+// two widest layers + eq levels
+size_t logup_arena_bytes(uint32_t top_log) {
+    const uint64_t L = 1ull << top_log;
+    return (size_t)32 * (5 * (L + L / 2) + 4 * L) + ((size_t)64 << 20);
+}
+
+// LogupMainphaseProtocol::prove (logup_mainphase.rs:156-208) over a tree of logup_build; `claim` = the expected sum of the fractions.
+// The tree is read, not consumed.  The sumcheck objects report through shared_pinned(): the caller sets it.
+int32_t logup_prove(Tape* tr, const LogupTree& tree, const Fr& claim, Arena* arena, hipStream_t s, std::vector<Claims>* out) {
+    const Fr* nd = tree.total;
+    GM_REQUIRE(!fr_is_zero(nd[1]), "logup denominator is zero (logup_mainphase.rs:161)");
+    GM_REQUIRE(fr_eq(nd[0], fr_mul(nd[1], claim)), "logup total does not match the claimed sum: num != denom * claim (logup_mainphase.rs:162)");
+    tr->write_scalars({nd[0], nd[1]});
+    std::vector<uint32_t> logsizes = tree.logsizes;
+    size_t left = tree.layers.size();
+    uint32_t curr_log = 0;
+    Claims running;
+    running.evs = {nd[0], nd[1]};
+    std::vector<Claims> accumulated;
+    Claims last;
+    const gm_fn f_logup = mkfn(GM_FN_LOGUP_LAYER, 1);
+    for (;;) {
+        const uint32_t incoming = logsizes.back();
+        GM_REQUIRE(left >= 2, "logup witness exhausted");
+        const LogupFrac& rr = tree.layers[left - 1];
+        const LogupFrac& ll = tree.layers[left - 2];
+        left -= 2;
+        GM_REQUIRE(ll.len == (1ull << curr_log) && rr.len == ll.len, "logup layer size mismatch");
+        Claims c4 = running;
+        if (curr_log == 0) {
+            // DenseEqSumcheck over zero variables (sumcheck.rs:844-872): gamma is drawn, no rounds, the four values are sent
+            Fr g0;
+            TRY(tr->challenge(&g0));
+            const std::vector<Fr> v = {ll.h_num, ll.h_den, rr.h_num, rr.h_den};
+            tr->write_scalars(v);
+            c4.point.clear();
+            c4.evs = v;
+        } else {
+            arena->reset();
+            ArenaScope scope(arena);
+            Advice adv;
+            adv.kind = Advice::DENSE;
+            adv.len = ll.len;
+            for (const Fr* ptr : {ll.num, ll.den, rr.num, rr.den}) {
+                adv.cols.emplace_back(new DevBuf());
+                adv.cols.back()->p = const_cast<Fr*>(ptr);   // borrowed view
+                adv.cols.back()->owned = false;
+                adv.cols.back()->bytes = ll.len * sizeof(Fr);
+            }
+            TRY(dense_deg2_prove(tr, f_logup, curr_log, &c4, adv, s));
+        }
+        if (incoming == curr_log) {
+            if (logsizes.size() == 2) { last = c4; break; }
+            running.point = c4.point;
+            running.evs = {c4.evs[0], c4.evs[1]};
+            Claims a;
+            a.point = c4.point;
+            a.evs = {c4.evs[2], c4.evs[3]};
+            accumulated.push_back(a);
+            logsizes.pop_back();
+        } else {
+            running = c4;
+            TRY(split_at_prove(tr, &running, true, 0, 2));
+            curr_log++;
+        }
+    }
+    accumulated.push_back(last);
+    std::reverse(accumulated.begin(), accumulated.end());
+    *out = accumulated;
     return GM_OK;
 }
 
@@ -1268,113 +1335,28 @@ int32_t pushforward_prove(const gm_msm_plan* plan, const uint64_t* d_points_xy, 
     const Fr supp_total = fr_mul(fr_from_u64(2 * (M - msize)), fr_inv(tau_s));
 
     // ---- LogupMainphaseProtocol::make_witness (logup_mainphase.rs:83-143) over logsizes [mlog-1, mlog-1, x_log, d_log]
-    std::vector<Frac> inputs(4), layers;
-    inputs[0].num = num->fr(); inputs[0].den = den->fr(); inputs[0].len = M / 2; inputs[0].keep_n = num; inputs[0].keep_d = den;
-    inputs[1].num = num->fr() + M / 2; inputs[1].den = den->fr() + M / 2; inputs[1].len = M / 2; inputs[1].keep_n = num; inputs[1].keep_d = den;
-    inputs[2].num = ac_c->fr(); inputs[2].den = table_c->fr(); inputs[2].len = X; inputs[2].keep_n = ac_c; inputs[2].keep_d = table_c;
-    inputs[3].num = ac_d->fr(); inputs[3].den = table_d->fr(); inputs[3].len = D; inputs[3].keep_n = ac_d; inputs[3].keep_d = table_d;
-    std::vector<uint32_t> logsizes = {mlog - 1, mlog - 1, x_log, d_log};
     GM_REQUIRE(mlog - 1 >= x_log && x_log >= d_log, "logsizes must be non-increasing (logup_mainphase.rs:75-77)");
-    size_t next_in = 2;
-    layers.push_back(inputs[0]);
-    layers.push_back(inputs[1]);
-    const SegPlan logup = plan_of(mkfn(GM_FN_LOGUP_LAYER, 1));
-    for (size_t i = 0;; i += 2) {
-        const uint64_t next_size = next_in < inputs.size() ? inputs[next_in].len : 1;
-        const uint64_t curr = layers[i].len;
-        Frac o;
-        o.len = curr;
-        TRY(mk(curr, &o.keep_n)); TRY(mk(curr, &o.keep_d));
-        o.num = o.keep_n->fr(); o.den = o.keep_d->fr();
-        const Fr* in[4] = {layers[i].num, layers[i].den, layers[i + 1].num, layers[i + 1].den};
-        Fr* outp[2] = {o.keep_n->fr(), o.keep_d->fr()};
-        TRY(launch_dense_map(logup, in, outp, curr, s));
-        if (curr == next_size) {
-            layers.push_back(o);
-            if (next_in < inputs.size()) layers.push_back(inputs[next_in++]);
-            else break;
-        } else {
-            GM_REQUIRE(curr > next_size, "logup witness: unreachable size order");
-            Frac lo = o, hi = o;
-            lo.len = hi.len = curr / 2;
-            hi.num = o.num + curr / 2; hi.den = o.den + curr / 2;
-            layers.push_back(lo);
-            layers.push_back(hi);
-        }
-    }
-    Frac top = layers.back();
-    layers.pop_back();
-    GM_REQUIRE(top.len == 1, "logup witness does not end in a single fraction");
-    Fr nd[2];
-    TRY(read_fr(top.num, &nd[0], s));
-    TRY(read_fr(top.den, &nd[1], s));
-    GM_REQUIRE(!fr_is_zero(nd[1]), "logup denominator is zero (logup_mainphase.rs:161)");
-    GM_REQUIRE(fr_eq(nd[0], fr_mul(nd[1], supp_total)), "logup total does not match the suppression term (logup_mainphase.rs:162)");
-    tr->write_scalars({nd[0], nd[1]});
+    const std::vector<uint32_t> logsizes = {mlog - 1, mlog - 1, x_log, d_log};
+    std::vector<LogupFrac> inputs(4);
+    inputs[0].num = num->fr(); inputs[0].den = den->fr(); inputs[0].len = M / 2;
+    inputs[1].num = num->fr() + M / 2; inputs[1].den = den->fr() + M / 2; inputs[1].len = M / 2;
+    inputs[2].num = ac_c->fr(); inputs[2].den = table_c->fr(); inputs[2].len = X;
+    inputs[3].num = ac_d->fr(); inputs[3].den = table_d->fr(); inputs[3].len = D;
+    LogupTree tree;
+    TRY(logup_build(inputs, logsizes, &tree, s));
 
     pf_timer.mark("logup witness");
     // workspace of the sumcheck objects: fold buffers of the widest layer + eq levels
     Arena arena;
-    TRY(arena.init((size_t)32 * (5 * (M / 2 + M / 4) + 2 * M) + ((size_t)64 << 20)));
+    TRY(arena.init(logup_arena_bytes(mlog - 1)));
     pf_timer.mark("arena");
     Fr* pinned = nullptr;
     TRY(thread_pinned_staging(&pinned));
     SharedPinnedScope pinned_scope(pinned);
 
     // ---- LogupMainphaseProtocol::prove (logup_mainphase.rs:156-208)
-    uint32_t curr_log = 0;
-    Claims running;
-    running.evs = {nd[0], nd[1]};
     std::vector<Claims> accumulated;
-    Claims last;
-    const gm_fn f_logup = mkfn(GM_FN_LOGUP_LAYER, 1);
-    for (;;) {
-        const uint32_t incoming = logsizes.back();
-        GM_REQUIRE(layers.size() >= 2, "logup witness exhausted");
-        const Frac rr = layers.back(); layers.pop_back();
-        const Frac ll = layers.back(); layers.pop_back();
-        GM_REQUIRE(ll.len == (1ull << curr_log) && rr.len == ll.len, "logup layer size mismatch");
-        Claims c4 = running;
-        if (curr_log == 0) {
-            // DenseEqSumcheck over zero variables (sumcheck.rs:844-872): gamma is drawn, no rounds, the four values are sent
-            Fr g0;
-            TRY(tr->challenge(&g0));
-            std::vector<Fr> v(4);
-            TRY(read_fr(ll.num, &v[0], s)); TRY(read_fr(ll.den, &v[1], s)); TRY(read_fr(rr.num, &v[2], s)); TRY(read_fr(rr.den, &v[3], s));
-            tr->write_scalars(v);
-            c4.point.clear();
-            c4.evs = v;
-        } else {
-            arena.reset();
-            ArenaScope scope(&arena);
-            Advice adv;
-            adv.kind = Advice::DENSE;
-            adv.len = ll.len;
-            for (const Fr* ptr : {ll.num, ll.den, rr.num, rr.den}) {
-                adv.cols.emplace_back(new DevBuf());
-                adv.cols.back()->p = const_cast<Fr*>(ptr);   // borrowed view
-                adv.cols.back()->owned = false;
-                adv.cols.back()->bytes = ll.len * sizeof(Fr);
-            }
-            TRY(dense_deg2_prove(tr, f_logup, curr_log, &c4, adv, s));
-        }
-        if (incoming == curr_log) {
-            if (logsizes.size() == 2) { last = c4; break; }
-            running.point = c4.point;
-            running.evs = {c4.evs[0], c4.evs[1]};
-            Claims a;
-            a.point = c4.point;
-            a.evs = {c4.evs[2], c4.evs[3]};
-            accumulated.push_back(a);
-            logsizes.pop_back();
-        } else {
-            running = c4;
-            TRY(split_at_prove(tr, &running, true, 0, 2));
-            curr_log++;
-        }
-    }
-    accumulated.push_back(last);
-    std::reverse(accumulated.begin(), accumulated.end());
+    TRY(logup_prove(tr, tree, supp_total, &arena, s, &accumulated));
     GM_REQUIRE(accumulated.size() == 3, "logup main phase must end with 3 claims");
     Claims cd = accumulated[0];
     *out_ac_c = accumulated[1];
@@ -1469,6 +1451,96 @@ int32_t pushforward_prove(const gm_msm_plan* plan, const uint64_t* d_points_xy, 
 }
 
 }  // namespace
+
+// =================================================================================================================
+// LogupMainphaseProtocol on its own (logup_mainphase.rs:66-242): the fraction tree over the caller's (numerator, denominator)
+// columns and its prover -- logup_build / logup_prove, the code the pushforward argument above runs.
+struct gm_logup_witness {
+    LogupTree tree;
+    Arena arena;
+    hipStream_t stream = nullptr;
+};
+
+extern "C" int32_t gm_logup_witness_create(const uint32_t* h_logsizes, uint32_t n_inputs, const uint64_t* const* d_num,
+                                           const uint64_t* const* d_den, gm_logup_witness** out, void* stream) {
+    GM_REQUIRE(out && d_num && d_den, "null argument");
+    *out = nullptr;
+    TRY(logup_shape_check(h_logsizes, n_inputs));
+    std::vector<LogupFrac> inputs(n_inputs);
+    for (uint32_t i = 0; i < n_inputs; i++) {
+        GM_REQUIRE(d_num[i] && d_den[i], "logup: input %u has a null column", i);
+        inputs[i].num = reinterpret_cast<const Fr*>(d_num[i]);
+        inputs[i].den = reinterpret_cast<const Fr*>(d_den[i]);
+        inputs[i].len = 1ull << h_logsizes[i];
+    }
+    std::unique_ptr<gm_logup_witness> w(new gm_logup_witness());
+    w->stream = as_stream(stream);
+    TRY(logup_build(inputs, std::vector<uint32_t>(h_logsizes, h_logsizes + n_inputs), &w->tree, w->stream));
+    GM_REQUIRE(!fr_is_zero(w->tree.total[1]), "logup denominator is zero (logup_mainphase.rs:161)");
+    if (h_logsizes[0]) TRY(w->arena.init(logup_arena_bytes(h_logsizes[0])));   // all layers of zero variables: no sumcheck object
+    *out = w.release();
+    return GM_OK;
+}
+
+extern "C" int32_t gm_logup_witness_total(const gm_logup_witness* w, uint64_t* h_num, uint64_t* h_den) {
+    GM_REQUIRE(w && h_num && h_den, "null argument");
+    memcpy(h_num, &w->tree.total[0], sizeof(Fr));
+    memcpy(h_den, &w->tree.total[1], sizeof(Fr));
+    return GM_OK;
+}
+
+extern "C" int32_t gm_logup_witness_destroy(gm_logup_witness* w) {
+    delete w;
+    return GM_OK;
+}
+
+static int32_t logup_prove_entry(const gm_logup_witness* w, const uint64_t* h_claim, const uint64_t* h_tape, uint64_t n_tape,
+                                 const gm_transcript* cb, uint64_t* h_msgs, uint64_t msgs_cap, uint64_t* n_msgs, uint64_t* h_points,
+                                 uint64_t* h_evs, uint64_t* tape_used, uint64_t* rounds) {
+    std::vector<Fr> msgs;
+    Tape tr{h_tape, n_tape, 0, &msgs, 0, cb, 0};
+    Fr claim;
+    memcpy(&claim, h_claim, sizeof(Fr));
+    Fr* pinned = nullptr;
+    TRY(thread_pinned_staging(&pinned));
+    SharedPinnedScope pinned_scope(pinned);
+    std::vector<Claims> groups;
+    TRY(logup_prove(&tr, w->tree, claim, const_cast<Arena*>(&w->arena), w->stream, &groups));
+    if (n_msgs) *n_msgs = msgs.size();
+    if (h_msgs) {
+        GM_REQUIRE(msgs.size() <= msgs_cap, "message buffer too small: %zu > %llu", msgs.size(), (unsigned long long)msgs_cap);
+        memcpy(h_msgs, msgs.data(), msgs.size() * sizeof(Fr));
+    }
+    // ClaimsAfter (logup_mainphase.rs:197): group 0 about inputs 0 and 1, group g >= 1 about input g + 1
+    GM_REQUIRE(groups.size() + 1 == w->tree.logsizes.size(), "logup main phase ended with %zu claim groups for %zu inputs", groups.size(),
+               w->tree.logsizes.size());
+    size_t np = 0, ne = 0;
+    for (size_t g = 0; g < groups.size(); g++) {
+        const Claims& c = groups[g];
+        GM_REQUIRE(c.point.size() == w->tree.logsizes[g ? g + 1 : 0] && c.evs.size() == (g ? 2u : 4u), "logup claim group %zu has the wrong shape", g);
+        if (h_points && !c.point.empty()) memcpy(h_points + 4 * np, c.point.data(), c.point.size() * sizeof(Fr));
+        if (h_evs) memcpy(h_evs + 4 * ne, c.evs.data(), c.evs.size() * sizeof(Fr));
+        np += c.point.size();
+        ne += c.evs.size();
+    }
+    if (tr.cb_rc) return set_err(GM_ERR_STATE, "transcript write_scalars callback failed with %d", tr.cb_rc);
+    if (tape_used) *tape_used = tr.pos;
+    if (rounds) *rounds = tr.rounds;
+    return GM_OK;
+}
+
+extern "C" int32_t gm_logup_prove(const gm_logup_witness* w, const uint64_t* h_claim, const uint64_t* h_tape, uint64_t n_tape,
+                                  uint64_t* h_msgs, uint64_t msgs_cap, uint64_t* n_msgs, uint64_t* h_points, uint64_t* h_evs,
+                                  uint64_t* tape_used, uint64_t* rounds) {
+    GM_REQUIRE(w && h_claim && (h_tape || !n_tape), "null argument");
+    return logup_prove_entry(w, h_claim, h_tape, n_tape, nullptr, h_msgs, msgs_cap, n_msgs, h_points, h_evs, tape_used, rounds);
+}
+
+extern "C" int32_t gm_logup_prove_tr(const gm_logup_witness* w, const uint64_t* h_claim, const gm_transcript* tr, uint64_t* h_points,
+                                     uint64_t* h_evs, uint64_t* n_challenges, uint64_t* rounds) {
+    GM_REQUIRE(w && h_claim && tr && tr->challenge, "null argument");
+    return logup_prove_entry(w, h_claim, nullptr, 0, tr, nullptr, 0, nullptr, h_points, h_evs, n_challenges, rounds);
+}
 
 // =================================================================================================================
 // The same argument with the matrix sharded by windows.  Every array of the argument is indexed (y, x) with the window

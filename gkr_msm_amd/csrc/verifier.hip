@@ -11,6 +11,7 @@
 
 #include "common.hpp"
 #include "gkr_layers.hpp"
+#include "logup.hpp"
 #include "pairing.hpp"
 
 using namespace gm;
@@ -727,5 +728,65 @@ extern "C" int32_t gm_gkr_verify_tr(const gm_gkr_layer* layers, uint32_t n_layer
                               h_final_evs, n_final_evs);
     } catch (const std::exception& e) {
         return set_err(GM_ERR_INVALID, "gm_gkr_verify_tr: %s", e.what());
+    }
+}
+
+// =================================================================================================================
+// LogupMainphaseProtocol::verify (logup_mainphase.rs:202-241) on its own: logup_verify above behind the shape check the prover runs
+// (gm_logup_witness_create).  Claims out as gm_logup_prove writes them.
+namespace {
+
+int32_t logup_verify_entry(Reader* rd, const uint32_t* h_logsizes, uint32_t n_inputs, const uint64_t* h_claim, uint64_t* h_points,
+                           uint64_t* h_evs) {
+    TRY(logup_shape_check(h_logsizes, n_inputs));
+    GM_REQUIRE(h_claim, "null argument");
+    Fr claim;
+    memcpy(&claim, h_claim, sizeof(Fr));
+    std::vector<VClaims> groups;
+    TRY(logup_verify(rd, std::vector<uint32_t>(h_logsizes, h_logsizes + n_inputs), claim, &groups));
+    VERIFY(groups.size() + 1 == n_inputs, "logup: %zu claim groups for %u inputs", groups.size(), n_inputs);
+    size_t np = 0, ne = 0;
+    for (size_t g = 0; g < groups.size(); g++) {
+        const VClaims& c = groups[g];
+        VERIFY(c.point.size() == h_logsizes[g ? g + 1 : 0] && c.evs.size() == (g ? 2u : 4u), "logup: claim group %zu has the wrong shape", g);
+        if (h_points && !c.point.empty()) memcpy(h_points + 4 * np, c.point.data(), c.point.size() * sizeof(Fr));
+        if (h_evs) memcpy(h_evs + 4 * ne, c.evs.data(), c.evs.size() * sizeof(Fr));
+        np += c.point.size();
+        ne += c.evs.size();
+    }
+    return GM_OK;
+}
+
+}  // namespace
+
+extern "C" int32_t gm_logup_verify(const uint32_t* h_logsizes, uint32_t n_inputs, const uint64_t* h_claim, const uint64_t* h_msgs,
+                                   uint64_t n_msgs, const uint64_t* h_tape, uint64_t n_tape, uint64_t* h_points, uint64_t* h_evs,
+                                   uint64_t* tape_used) {
+    try {
+        GM_REQUIRE((h_msgs || !n_msgs) && (h_tape || !n_tape), "null argument");
+        Reader rd;
+        rd.scalars = reinterpret_cast<const Fr*>(h_msgs);
+        rd.tape = h_tape;
+        rd.n_scalars = n_msgs; rd.n_tape = n_tape;
+        TRY(logup_verify_entry(&rd, h_logsizes, n_inputs, h_claim, h_points, h_evs));
+        if (rd.si != n_msgs)
+            return set_err(GM_ERR_VERIFY, "proof has unread messages (%llu of %llu scalars read)", (unsigned long long)rd.si,
+                           (unsigned long long)n_msgs);
+        if (tape_used) *tape_used = rd.pos;
+        return GM_OK;
+    } catch (const std::exception& e) {
+        return set_err(GM_ERR_INVALID, "gm_logup_verify: %s", e.what());
+    }
+}
+
+extern "C" int32_t gm_logup_verify_tr(const uint32_t* h_logsizes, uint32_t n_inputs, const uint64_t* h_claim,
+                                      const gm_transcript_reader* tr, uint64_t* h_points, uint64_t* h_evs) {
+    try {
+        GM_REQUIRE(tr && tr->read_scalars && tr->challenge, "null argument");
+        Reader rd;
+        rd.cb = tr;
+        return logup_verify_entry(&rd, h_logsizes, n_inputs, h_claim, h_points, h_evs);
+    } catch (const std::exception& e) {
+        return set_err(GM_ERR_INVALID, "gm_logup_verify_tr: %s", e.what());
     }
 }

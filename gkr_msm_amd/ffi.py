@@ -194,6 +194,15 @@ _SIGS = {
                                                  vp, vp, vp, vp, vp, vp, u64p, u64p, vp]),
     "gm_pushforward_prove_tr": (C.c_int32, [vp, vp, C.c_uint32, vp, vp, C.POINTER(GmTranscript), vp, vp, vp, vp, vp, vp, vp, u64p,
                                             u64p, vp]),
+    "gm_logup_witness_create": (C.c_int32, [vp, C.c_uint32, vp, vp, C.POINTER(vp), vp]),
+    "gm_logup_witness_total": (C.c_int32, [vp, vp, vp]),
+    "gm_logup_witness_destroy": (C.c_int32, [vp]),
+    "gm_logup_prove": (C.c_int32, [vp, vp, vp, C.c_uint64, vp, C.c_uint64, u64p, vp, vp, u64p, u64p]),
+    "gm_logup_prove_tr": (C.c_int32, [vp, vp, C.POINTER(GmTranscript), vp, vp, u64p, u64p]),
+    "gm_logup_verify": (C.c_int32, [vp, C.c_uint32, vp, vp, C.c_uint64, vp, C.c_uint64, vp, vp, u64p]),
+    "gm_logup_verify_tr": (C.c_int32, [vp, C.c_uint32, vp, C.POINTER(GmTranscriptReader), vp, vp]),
+    "gm_logup_multiplicities": (C.c_int32, [vp, C.c_uint64, C.c_uint64, vp, vp]),
+    "gm_logup_denominators": (C.c_int32, [C.c_uint32, vp, C.c_uint64, vp, vp, C.c_int32, vp, vp, vp]),
     "gm_multiopen_prove": (C.c_int32, [C.c_uint32, C.c_uint32, vp, vp, vp, vp, C.c_uint64, vp, C.c_uint64, u64p, vp, vp, u64p, u64p, vp]),
     "gm_multiopen_prove_tr": (C.c_int32, [C.c_uint32, C.c_uint32, vp, vp, vp, C.POINTER(GmTranscript), vp, vp, u64p, u64p, vp]),
     "gm_pippenger_last_spans": (C.c_int32, [C.POINTER(C.c_double)]),

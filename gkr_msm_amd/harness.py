@@ -1176,3 +1176,142 @@ def make_program(n_ins, n_outs, deg, terms):
 
 def destroy_program(pid):
     ffi.check(ffi.lib().gm_fn_program_destroy(pid))
+
+
+# ------------------------------------------------------------------ GKR-logup on the caller's fractions
+def _logup_groups(logsizes, pts, evs):
+    """flat points / evaluations of gm_logup_prove / gm_logup_verify -> ClaimsAfter: [(point, evs), ...]"""
+    out, ip, ie = [], 0, 0
+    for g, lg in enumerate([logsizes[0]] + list(logsizes[2:])):
+        ne = 4 if g == 0 else 2
+        out.append((pts[ip:ip + lg], evs[ie:ie + ne]))
+        ip, ie = ip + lg, ie + ne
+    return out
+
+
+def _logup_out(logsizes):
+    npts = logsizes[0] + sum(logsizes[2:])
+    return np.zeros((max(npts, 1), 4), dtype=np.uint64), np.zeros((2 * len(logsizes), 4), dtype=np.uint64), npts
+
+
+class LogupWitness:
+    """gm_logup_witness: the fraction tree of LogupMainphaseProtocol over (numerator, denominator) device columns + its prover"""
+
+    def __init__(self, logsizes, nums, dens):
+        self.L = ffi.lib()
+        self.logsizes = [int(v) for v in logsizes]
+        self.keep = (tuple(nums), tuple(dens))
+        self.h = C.c_void_p()
+        ls = np.asarray(self.logsizes, dtype=np.uint32)
+        ffi.check(self.L.gm_logup_witness_create(ls.ctypes.data, len(self.logsizes), ptr_array(nums), ptr_array(dens), C.byref(self.h),
+                                                 cur_stream()))
+
+    def close(self):
+        if self.h:
+            self.L.gm_logup_witness_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def total(self):
+        """the [num, den] make_witness returns, canonical ints"""
+        nd = np.zeros((2, 4), dtype=np.uint64)
+        ffi.check(self.L.gm_logup_witness_total(self.h, nd[0:1].ctypes.data, nd[1:2].ctypes.data))
+        return tuple(codec.from_mont_limbs(nd))
+
+    def prove_rc(self, claim, tape, msgs_cap=1 << 14):
+        """gm_logup_prove -> (rc, dict(msgs, claims, tape_used, rounds)); rc != 0 is returned, not raised"""
+        cl = fr_arg([claim])
+        tp = codec.ints_to_limbs(tape if tape else [0])
+        msgs = np.zeros((msgs_cap, 4), dtype=np.uint64)
+        pts, evs, npts = _logup_out(self.logsizes)
+        nm, used, rounds = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        rc = self.L.gm_logup_prove(self.h, cl.ctypes.data, tp.ctypes.data, len(tape), msgs.ctypes.data, msgs_cap, C.byref(nm),
+                                   pts.ctypes.data, evs.ctypes.data, C.byref(used), C.byref(rounds))
+        if rc:
+            return rc, None
+        return rc, dict(msgs=codec.from_mont_limbs(msgs[: nm.value]),
+                        claims=_logup_groups(self.logsizes, codec.from_mont_limbs(pts[:npts]), codec.from_mont_limbs(evs)),
+                        tape_used=used.value, rounds=rounds.value)
+
+    def prove(self, claim, tape, msgs_cap=1 << 14):
+        rc, out = self.prove_rc(claim, tape, msgs_cap)
+        ffi.check(rc)
+        return out
+
+    def prove_tr(self, claim, transcript):
+        """gm_logup_prove_tr under a live transcript (MerlinTranscript / LiveTranscript) -> dict(claims, n_challenges, rounds)"""
+        cl = fr_arg([claim])
+        pts, evs, npts = _logup_out(self.logsizes)
+        used, rounds = C.c_uint64(), C.c_uint64()
+        ffi.check(self.L.gm_logup_prove_tr(self.h, cl.ctypes.data, C.byref(transcript.c), pts.ctypes.data, evs.ctypes.data,
+                                           C.byref(used), C.byref(rounds)))
+        return dict(claims=_logup_groups(self.logsizes, codec.from_mont_limbs(pts[:npts]), codec.from_mont_limbs(evs)),
+                    n_challenges=used.value, rounds=rounds.value)
+
+
+def logup_verify(logsizes, claim, msgs, tape):
+    """gm_logup_verify over recorded messages and a challenge tape -> (rc, dict(claims, tape_used)); rc != 0 is returned, not raised"""
+    L = ffi.lib()
+    ls = np.asarray([int(v) for v in logsizes], dtype=np.uint32)
+    cl = fr_arg([claim])
+    m = fr_arg(msgs if msgs else [0])
+    tp = codec.ints_to_limbs(tape if tape else [0])
+    ok = len(ls) >= 2 and all(v <= 30 for v in ls)
+    pts, evs, npts = _logup_out([int(v) for v in ls]) if ok else (np.zeros((1, 4), dtype=np.uint64), np.zeros((2, 4), dtype=np.uint64), 0)
+    used = C.c_uint64()
+    rc = L.gm_logup_verify(ls.ctypes.data, len(ls), cl.ctypes.data, m.ctypes.data, len(msgs), tp.ctypes.data, len(tape), pts.ctypes.data,
+                           evs.ctypes.data, C.byref(used))
+    if rc:
+        return rc, None
+    return rc, dict(claims=_logup_groups(list(ls), codec.from_mont_limbs(pts[:npts]), codec.from_mont_limbs(evs)), tape_used=used.value)
+
+
+def logup_verify_merlin(logsizes, claim, proof, label=b"gkr-msm"):
+    """gm_logup_verify_tr over gm_merlin_create_verifier(proof) -> (rc, dict(claims, unread))"""
+    L = ffi.lib()
+    h = C.c_void_p()
+    pb = C.create_string_buffer(bytes(proof), max(len(proof), 1))
+    ffi.check(L.gm_merlin_create_verifier(label, len(label), pb, len(proof), C.byref(h)))
+    try:
+        rd = ffi.GmTranscriptReader()
+        ffi.check(L.gm_merlin_reader(h, C.byref(rd)))
+        ls = np.asarray([int(v) for v in logsizes], dtype=np.uint32)
+        cl = fr_arg([claim])
+        pts, evs, npts = _logup_out([int(v) for v in ls])
+        rc = L.gm_logup_verify_tr(ls.ctypes.data, len(ls), cl.ctypes.data, C.byref(rd), pts.ctypes.data, evs.ctypes.data)
+        left = C.c_uint64()
+        ffi.check(L.gm_merlin_unread(h, C.byref(left)))
+        if rc:
+            return rc, None
+        return rc, dict(claims=_logup_groups(list(ls), codec.from_mont_limbs(pts[:npts]), codec.from_mont_limbs(evs)), unread=left.value)
+    finally:
+        L.gm_merlin_destroy(h)
+
+
+def logup_multiplicities_rc(d_idx, n, table_len):
+    """gm_logup_multiplicities of an int32 CUDA tensor of indices -> (rc, int64 CUDA tensor of table_len Montgomery elements)"""
+    d_m = dev_empty(4 * table_len)
+    rc = ffi.lib().gm_logup_multiplicities(C.c_void_p(d_idx.data_ptr()) if n else None, n, table_len, _p(d_m), cur_stream())
+    return rc, d_m
+
+
+def logup_multiplicities(d_idx, n, table_len):
+    rc, d_m = logup_multiplicities_rc(d_idx, n, table_len)
+    ffi.check(rc)
+    return d_m
+
+
+def logup_denominators(cols, psi, tau, negate=False, ones=False):
+    """gm_logup_denominators: den[i] = +-(tau - sum_k psi^k cols[k][i]) -> (den, ones or None), CUDA tensors"""
+    n = cols[0].numel() // 4
+    d_den = dev_empty(4 * n)
+    d_ones = dev_empty(4 * n) if ones else None
+    ps, ta = fr_arg([psi]), fr_arg([tau])
+    ffi.check(ffi.lib().gm_logup_denominators(len(cols), ptr_array(cols), n, ps.ctypes.data, ta.ctypes.data, 1 if negate else 0, _p(d_den),
+                                              _p(d_ones), cur_stream()))
+    return d_den, d_ones

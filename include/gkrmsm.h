@@ -655,7 +655,54 @@ int32_t gm_pushforward_prove_tr(const gm_msm_plan* plan, const uint64_t* d_point
                                 uint64_t* h_ac_c_evs, uint64_t* h_ac_d_point, uint64_t* h_ac_d_evs, uint64_t* n_challenges,
                                 uint64_t* rounds, void* stream);
 
-/* MultiOpenReduction::prove (cleanup/protocols/multiopen_reduction.rs:65-93; the first step of the "open" span, pippenger.rs:222-258):
+/* ---------------------------------------------------------------- GKR-logup on the caller's fractions
+ * LogupMainphaseProtocol (pushforward/logup_mainphase.rs:66-242) on its own: prove that sum_i sum_j num_i[j] / den_i[j] = claim for
+ * n_inputs (numerator, denominator) pairs of device columns, pair i of 2^logsizes[i] elements.  The pushforward argument above runs
+ * the same code over its four inputs.
+ *   shape rules (the reference's asserts :76-80 and this library's bounds; GM_ERR_INVALID naming the rule, checked before any device
+ *   work, by the prover and the verifier alike): 2 <= n_inputs <= 64, logsizes non-increasing, logsizes[0] == logsizes[1], every
+ *   logsize <= 30.  Logsize 0 is legal, also for the first two ([0, 0] is a one-layer proof with no rounds).
+ *   gm_logup_witness_create  LogupMainphaseProtocol::new + make_witness (:75-137): the fraction tree.  The columns are borrowed, never
+ *                            written, and must outlive the witness; the witness owns every level of the tree and nothing of the
+ *                            inputs.  A zero total denominator is GM_ERR_INVALID.  Synchronises the stream.
+ *   gm_logup_witness_total   the [num, den] the reference's make_witness returns (Montgomery)
+ *   gm_logup_prove(_tr)      LogupMainphaseProtocol::prove (:149-200) over a challenge tape / under a live transcript.  h_claim = the
+ *                            expected sum; num != den * claim is GM_ERR_INVALID with nothing written.  The witness is not consumed:
+ *                            a second call with the same tape repeats the messages.  One call at a time per witness.
+ *                            Messages: [num, den], then per step a DenseEqSumcheck of LogupLayerFn (zero variables: gamma is drawn,
+ *                            no rounds, the four values are written), then the hand-over to the next input or SplitAt(HI(0), 2).
+ *   claims out = ClaimsAfter in the reference's order (:197): group 0 is about inputs 0 and 1 -- a point of logsizes[0] coordinates
+ *                            and [num0, den0, num1, den1]; group g >= 1 about input g + 1 -- a point of logsizes[g + 1] coordinates
+ *                            and [num, den].  h_points = the groups' points back to back (logsizes[0] + sum_{i >= 2} logsizes[i]
+ *                            elements), h_evs = 2 n_inputs elements.
+ *   gm_logup_verify(_tr)     LogupMainphaseProtocol::verify (:202-241), host only: GM_ERR_VERIFY for a zero denominator, num != den *
+ *                            claim or a failed layer; the recorded form also insists that every message was read. */
+typedef struct gm_logup_witness gm_logup_witness;
+int32_t gm_logup_witness_create(const uint32_t* h_logsizes, uint32_t n_inputs, const uint64_t* const* d_num,
+                                const uint64_t* const* d_den, gm_logup_witness** out, void* stream);
+int32_t gm_logup_witness_total(const gm_logup_witness* w, uint64_t* h_num, uint64_t* h_den);
+int32_t gm_logup_witness_destroy(gm_logup_witness* w);
+int32_t gm_logup_prove(const gm_logup_witness* w, const uint64_t* h_claim, const uint64_t* h_tape, uint64_t n_tape,
+                       uint64_t* h_msgs, uint64_t msgs_cap, uint64_t* n_msgs, uint64_t* h_points, uint64_t* h_evs,
+                       uint64_t* tape_used, uint64_t* rounds);
+int32_t gm_logup_prove_tr(const gm_logup_witness* w, const uint64_t* h_claim, const gm_transcript* tr, uint64_t* h_points,
+                          uint64_t* h_evs, uint64_t* n_challenges, uint64_t* rounds);
+int32_t gm_logup_verify(const uint32_t* h_logsizes, uint32_t n_inputs, const uint64_t* h_claim, const uint64_t* h_msgs,
+                        uint64_t n_msgs, const uint64_t* h_tape, uint64_t n_tape, uint64_t* h_points, uint64_t* h_evs,
+                        uint64_t* tape_used);
+int32_t gm_logup_verify_tr(const uint32_t* h_logsizes, uint32_t n_inputs, const uint64_t* h_claim,
+                           const gm_transcript_reader* tr, uint64_t* h_points, uint64_t* h_evs);
+/* The two columns a lookup argument builds before the tree ("a lookup with gm_logup"):
+ *   gm_logup_multiplicities  m[j] = #{ i < n : idx[i] == j } as field elements (Montgomery), j < table_len; n < 2^32.  An index >=
+ *                            table_len is GM_ERR_INVALID (found on the device, reported after the launch; d_m is then unspecified).
+ *                            Exact integer counters: the result does not depend on the order of the adds.  Synchronises the stream.
+ *   gm_logup_denominators    den[i] = tau - sum_k psi^k col_k[i] (negate != 0: its negative), i < len; d_ones, if not NULL, is filled
+ *                            with 1.  k <= 8 columns; Horner in psi, highest column first.  h_psi / h_tau: Montgomery. */
+int32_t gm_logup_multiplicities(const uint32_t* d_idx, uint64_t n, uint64_t table_len, uint64_t* d_m, void* stream);
+int32_t gm_logup_denominators(uint32_t k, const uint64_t* const* d_cols, uint64_t len, const uint64_t* h_psi,
+                              const uint64_t* h_tau, int32_t negate, uint64_t* d_den, uint64_t* d_ones, void* stream);
+
+/* MultiOpenReduction::prove(cleanup/protocols/multiopen_reduction.rs:65-93; the first step of the "open" span, pippenger.rs:222-258):
  * nargs (<= 8) device columns of 2^nvars elements with one claim each -- h_points: nargs x nvars coordinates, h_evs: nargs
  * evaluations -- are reduced to nargs claims at one common point (h_out_point: nvars coordinates, h_out_evs: nargs evaluations). */
 int32_t gm_multiopen_prove(uint32_t nvars, uint32_t nargs, const uint64_t* const* d_polys, const uint64_t* h_points,
